@@ -15,8 +15,11 @@ each shard's stream is fixed at 1M activations); the invoker health vector is al
 `python bench.py --gpus N` with no torch.distributed environment starts the N ranks itself (torch.distributed.run as
 a child process, before this process touches any GPU); the driver may also launch it under torch.distributed.run.
 
-Prints ONE JSON line on rank 0.  The value counts only when every rank's assignment vector, flags and final permits
-are bit-exact with the CPU oracle (checked after timing).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes the last step's outputs when
+--dump-outputs is given, and prints the line.  --full adds, after the timed steps, everything else the line can hold:
+the bit-exact check of every rank's assignment vector, flags and final permits against the CPU oracle (the value is
+0 when it fails), the engine kernel's own time and the HBM roofline, the host-buffer (PCIe-inclusive) replay, the
+shim-path legs and the CPU baseline; --no-check, --no-h2d, --no-shim-path and --no-cpu-baseline drop single legs of it.
 """
 import argparse
 import hashlib
@@ -48,11 +51,20 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="headline", help="headline (= c5 shards for N > 1) | c1 | c2 | c2_64k | c3 | c4")
     ap.add_argument("--n-activations", type=int, default=None, help="per shard (default: the config's, 1M)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the host-buffer (PCIe-inclusive) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the oracle check, the engine-kernel timing and roofline, the "
+                         "host-buffer replay, the shim-path legs and the CPU baseline (a plain run reports them as null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (per shard: assignment vector, decision flags, "
+                         "release flags, final permits) as DIR/<name>.npy in float32, at most 64 MB in all (a fixed, "
+                         "seeded sample of larger outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the oracle check")
+    ap.add_argument("--no-h2d", action="store_true",
+                    help="with --full: skip the host-buffer (PCIe-inclusive) measurement")
     ap.add_argument("--cpu-threads", type=int, default=16)
-    ap.add_argument("--no-shim-path", action="store_true", help="skip the shim-path leg (per-call latency)")
+    ap.add_argument("--no-shim-path", action="store_true",
+                    help="with --full: skip the shim-path leg (per-call latency)")
     ap.add_argument("--health-group", type=int, default=8,
                     help="per-batch health cadence: batches per engine launch (owgs_replay_device_group; 1 = one "
                          "owgs_update_health_device + owgs_replay_device_span per batch)")
@@ -78,7 +90,29 @@ def parse(argv=None):
                          "collective, streams and ordering on one GPU)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher/collective plumbing only (gloo, CPU): no replay, value null (tests)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files of all ranks together
+DUMP_SEED = 0xD0C5
+
+
+def dump_outputs(out_dir, arrays, n_arrays_total):
+    """Write `arrays` (name -> integer numpy array) as out_dir/<name>.npy in float32 (invoker indices, flags and
+    permits are far below 2^24, so the conversion is exact).  `n_arrays_total` arrays are written by all ranks
+    together; each gets an equal share of DUMP_MAX_BYTES, and a longer one is cut to a fixed sample: indices drawn
+    once from DUMP_SEED and the array's length, sorted, the same in every run and every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_MAX_BYTES // 4 // max(n_arrays_total, 1) - 32  # elements per array (32: room for the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if len(a) > cap:
+            idx = np.sort(np.random.Generator(np.random.PCG64([DUMP_SEED, len(a)])).choice(len(a), cap, replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
 
 
 def _free_port() -> int:
@@ -740,10 +774,21 @@ def main():
     replay_ms = float(np.mean([a.elapsed_time(c) for a, c in evs]))
     smode = b.stream_mode_stats()  # the replay ran through the resident engine's stream mode (OWGS_SPEC_REPLAY)
     stats = smode if smode is not None else b.stats()
+    if args.dump_outputs:  # what the last timed step left: the decisions a caller of the replay receives
+        arrays = {}
+        for sh in shards:
+            arrays[f"shard{sh.idx}_out_invoker"] = sh.d_out.cpu().numpy()
+            arrays[f"shard{sh.idx}_out_flags"] = sh.d_fl.cpu().numpy()
+            arrays[f"shard{sh.idx}_rel_flags"] = sh.d_rf.cpu().numpy()[: len(sh.s.rel_aid)]
+            arrays[f"shard{sh.idx}_permits"] = sh.b.permits()
+        dump_outputs(args.dump_outputs, arrays, 4 * K * world)
+    # everything below is measured or checked only with --full (a plain run reports it as null)
+    check = args.full and not args.no_check
+    h2d = args.full and not args.no_h2d and not per_batch
     # the dominant kernel alone: HIP events the library records around each engine launch on the replay stream,
     # read after instrumented replays outside the timed region (reading them inside would add a sync per step)
     eng = []
-    for _ in range(max(3, min(args.steps, 5))):
+    for _ in range(max(3, min(args.steps, 5)) if args.full else 0):
         if per_batch:  # one engine launch per batch: their durations add up to the step's kernel time
             tm = []
             launch_all(tm)
@@ -751,11 +796,11 @@ def main():
             continue
         launch_all()
         eng.append(float(np.mean([sh.b.engine_ms() for sh in shards[::MULTI_MAX]])))
-    kern_ms = float(np.mean(eng))
+    kern_ms = float(np.mean(eng)) if eng else 0.0
 
     exact = True
     o_ref = None
-    if not args.no_check:
+    if check:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle as O
 
@@ -775,7 +820,7 @@ def main():
     # host buffers through the C ABI (owgs_replay: argument checks, H2D of the stream, replay, D2H of the decisions):
     # the rate a JVM caller handing over host arrays would see; never the bench value
     h2d_ms = 0.0
-    if not args.no_h2d and not per_batch:
+    if h2d:
         reps = 3
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -786,7 +831,7 @@ def main():
         h2d_ms = (time.perf_counter() - t1) / reps * 1e3
 
     shim = None
-    if world == 1 and K == 1 and not args.no_shim_path:
+    if args.full and world == 1 and K == 1 and not args.no_shim_path:
         shim = shim_path(w, o_ref, torch.cuda.current_device())
 
     n_dec = sum(len(sh.s.act) for sh in shards)  # this rank's decisions per step
@@ -796,14 +841,28 @@ def main():
         dist, [t_step, 0.0 if exact else 1.0, kern_ms, replay_ms, h2d_ms, disagree], dev)
     exact = bad == 0.0
     value = cluster.whole_job_rate(n_dec, world, t_step)
-    algo = algorithmic_bytes(w)
-    per_launch = min(K, MULTI_MAX)  # shards one engine launch replays
-    achieved = algo["survey"] * per_launch / (kern_ms * 1e-3) / 1e9
-    key = f"{args.config}|n{len(s.act)}|c{n_ctl}|s{args.slots}|k{per_launch}"
-    pmc = pmc_traffic(key)
+    roofline = None
+    if args.full:
+        algo = algorithmic_bytes(w)
+        per_launch = min(K, MULTI_MAX)  # shards one engine launch replays
+        achieved = algo["survey"] * per_launch / (kern_ms * 1e-3) / 1e9
+        key = f"{args.config}|n{len(s.act)}|c{n_ctl}|s{args.slots}|k{per_launch}"
+        pmc = pmc_traffic(key)
+        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": pmc["bytes"] if pmc else None,
+                    "traffic_source": pmc["source"] if pmc else f"no --pmc pass recorded for this build ({key})",
+                    # what limits this kernel instead: one CU's instruction issue along the decision chain
+                    "issue": pmc.get("issue") if pmc else None,
+                    "kernel": ("owgs_resident_kernel" if smode is not None else
+                               "owgs_engine_kernel" if K == 1 else "owgs_engine_multi_kernel"),
+                    "kernel_ms": kern_ms, "replay_ms": replay_ms, "shards_per_launch": per_launch,
+                    "algorithmic_bytes": algo["survey"] * per_launch,
+                    "algorithmic_def": f"SURVEY 8(d): {B_DECISION} B/decision + {B_RELEASE} B/release",
+                    "achieved_stream_bytes": algo["stream"] * per_launch / (kern_ms * 1e-3) / 1e9}
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args, w, n_ctl, shard_ids[0])
         line = {
             "metric": "scheduling decisions/sec (whole node) at 10k invokers, 1M-activation batch",
@@ -818,7 +877,8 @@ def main():
             "vs_baseline": None,
             "dtype": "int32",
             "data": "synthetic (workload.py, seeded Zipf stream)",
-            "bit_exact": exact,
+            "bit_exact": exact if args.full else None,  # null: a plain run does not check
+            "full": args.full,
             "config": {"workload": args.config, "invokers": int(len(w.inv_ids)), "activations_per_shard": len(s.act),
                        "batches": s.n_batches, "batch": w.info["batch"], "releases": int(len(s.rel_aid)),
                        "cluster_size": n_ctl, "slots": args.slots, "shards": shard_ids if world == 1 else None,
@@ -836,19 +896,8 @@ def main():
                        "health_exchange": ("RCCL all_gather_into_tensor" if hx.collective else
                                            "local copy (one rank, no process group)"),
                        "parallelism": f"{n_ctl} controller shard(s), {K} per GPU, {world} GPU(s)"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": pmc["bytes"] if pmc else None,
-                         "traffic_source": pmc["source"] if pmc else f"no --pmc pass recorded for this build ({key})",
-                         # what limits this kernel instead: one CU's instruction issue along the decision chain
-                         "issue": pmc.get("issue") if pmc else None,
-                         "kernel": ("owgs_resident_kernel" if smode is not None else
-                                    "owgs_engine_kernel" if K == 1 else "owgs_engine_multi_kernel"),
-                         "kernel_ms": kern_ms, "replay_ms": replay_ms, "shards_per_launch": per_launch,
-                         "algorithmic_bytes": algo["survey"] * per_launch,
-                         "algorithmic_def": f"SURVEY 8(d): {B_DECISION} B/decision + {B_RELEASE} B/release",
-                         "achieved_stream_bytes": algo["stream"] * per_launch / (kern_ms * 1e-3) / 1e9},
-            "h2d_inclusive": None if (args.no_h2d or per_batch) else {
+            "roofline": roofline,
+            "h2d_inclusive": None if not h2d else {
                 "value": world * n_dec / (h2d_ms * 1e-3), "unit": "decisions/s", "ms_per_step": h2d_ms,
                 "path": "owgs_replay host ABI: host checks + H2D stream + replay + D2H decisions"},
             "shim_path": shim,

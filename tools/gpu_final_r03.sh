@@ -38,7 +38,7 @@ for s in $STEPS; do
       rc=$?; tail -3 $O/sq.log; [ $rc -eq 0 ] || stop sq $rc
       cp gpurun_out/pmc/summary.txt $O/sq_pmc.txt ;;
     bench)
-      timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err
+      timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err
       rc=$?; cut -c1-300 $O/bench.json; [ $rc -eq 0 ] || { tail -20 $O/bench.err; stop bench $rc; } ;;
     prof)
       rm -rf $O/prof
@@ -48,13 +48,13 @@ for s in $STEPS; do
     cfgs)  # one bench line per config (own cpu baseline): configs[1..3] and configs[4] shards at clusterSize 2, 4, 8
       rm -f $O/cfgs.jsonl
       for c in "--config c2" "--config c2_64k" "--config c3" "--config c4" "--cluster-size 2" "--cluster-size 4" "--cluster-size 8"; do
-        timeout -k 10 400 python bench.py $c --steps 5 --warmup 1 --no-h2d --no-shim-path >> $O/cfgs.jsonl 2>> $O/cfgs.err
+        timeout -k 10 400 python bench.py --full $c --steps 5 --warmup 1 --no-h2d --no-shim-path >> $O/cfgs.jsonl 2>> $O/cfgs.err
         rc=$?; tail -1 $O/cfgs.jsonl | cut -c1-160; [ $rc -eq 0 ] || { tail -20 $O/cfgs.err; stop "cfg $c" $rc; }
       done ;;
     churn)  # configs[4] cadence on one GPU: health all-gathered and applied before every batch
       rm -f $O/churn.jsonl
       for c in "" "--cluster-size 8"; do
-        timeout -k 10 400 python bench.py --health-churn $c --steps 3 --warmup 1 --no-shim-path --no-cpu-baseline >> $O/churn.jsonl 2>> $O/churn.err
+        timeout -k 10 400 python bench.py --full --health-churn $c --steps 3 --warmup 1 --no-shim-path --no-cpu-baseline >> $O/churn.jsonl 2>> $O/churn.err
         rc=$?; tail -1 $O/churn.jsonl | cut -c1-160; [ $rc -eq 0 ] || { tail -20 $O/churn.err; stop "churn $c" $rc; }
       done ;;
     shimprof)  # kernel trace of the shim path (owgs_process_batch at drain 512)

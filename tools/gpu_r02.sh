@@ -15,11 +15,11 @@ for s in ${STEPS:-tests bench cfgs phases}; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
       rc=$?; tail -2 $O/smoke.log; [ $rc -eq 0 ] || stop smoke $rc ;;
     bench)
-      timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err
+      timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err
       rc=$?; cut -c1-600 $O/bench.json; [ $rc -eq 0 ] || { tail -20 $O/bench.err; stop bench $rc; } ;;
     cfgs)  # one bench line per config (own cpu baseline): configs[1..3] and configs[4] shards at clusterSize 2, 4, 8
       for c in "--config c2" "--config c3" "--config c4" "--cluster-size 2" "--cluster-size 4" "--cluster-size 8"; do
-        timeout -k 10 400 python bench.py $c --steps 5 --warmup 1 --no-h2d ${CFG_ARGS:-} >> $O/cfgs.jsonl 2>> $O/cfgs.err
+        timeout -k 10 400 python bench.py --full $c --steps 5 --warmup 1 --no-h2d ${CFG_ARGS:-} >> $O/cfgs.jsonl 2>> $O/cfgs.err
         rc=$?; tail -1 $O/cfgs.jsonl | cut -c1-300; [ $rc -eq 0 ] || { tail -20 $O/cfgs.err; stop "cfg $c" $rc; }
       done ;;
     phases)

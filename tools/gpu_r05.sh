@@ -25,7 +25,7 @@ for s in ${STEPS:-tests}; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
       rc=$?; tail -1 $O/smoke.log; [ $rc -eq 0 ] || stop smoke $rc ;;
     bench)
-      timeout -k 10 400 python bench.py ${BENCHARGS} > $O/bench.json 2> $O/bench.err
+      timeout -k 10 400 python bench.py --full ${BENCHARGS} > $O/bench.json 2> $O/bench.err
       rc=$?; cut -c1-400 $O/bench.json; [ $rc -eq 0 ] || { tail -20 $O/bench.err; stop bench $rc; } ;;
     prof)
       rm -rf $O/prof
@@ -35,7 +35,7 @@ for s in ${STEPS:-tests}; do
     cfgs)
       rm -f $O/cfgs.jsonl
       for c in "--config c2" "--config c2_64k" "--config c3" "--config c4" "--cluster-size 2" "--cluster-size 4" "--cluster-size 8"; do
-        timeout -k 10 400 python bench.py $c --steps 5 --warmup 1 --no-h2d --no-shim-path >> $O/cfgs.jsonl 2>> $O/cfgs.err
+        timeout -k 10 400 python bench.py --full $c --steps 5 --warmup 1 --no-h2d --no-shim-path >> $O/cfgs.jsonl 2>> $O/cfgs.err
         rc=$?; tail -1 $O/cfgs.jsonl | cut -c1-160; [ $rc -eq 0 ] || { tail -20 $O/cfgs.err; stop "cfg $c" $rc; }
       done ;;
     pmc)
@@ -102,7 +102,7 @@ for l in d['legs']:
       rm -f $O/churn.jsonl
       for c in "" "--cluster-size 8"; do
         for h in "" "--health-churn" "--health-churn --health-group 1"; do
-          timeout -k 10 400 python bench.py $h $c --steps 5 --warmup 1 --no-shim-path --no-cpu-baseline --no-h2d >> $O/churn.jsonl 2>> $O/churn.err
+          timeout -k 10 400 python bench.py --full $h $c --steps 5 --warmup 1 --no-shim-path --no-cpu-baseline --no-h2d >> $O/churn.jsonl 2>> $O/churn.err
           rc=$?; tail -1 $O/churn.jsonl | cut -c1-200; [ $rc -eq 0 ] || { tail -20 $O/churn.err; stop "churn $h $c" $rc; }
         done
       done ;;
