@@ -381,6 +381,21 @@ int owgs_engine_ms(owgs_ctx* ctx, float* ms);
  * existed (after owgs_update_cluster with activations in flight).  Returns the number of counters (55). */
 int owgs_resident_stats(owgs_ctx* ctx, int64_t* out, int32_t cap);
 
+/* Which path of the large-state engine (a pool beyond owgs_limits, or a maxConcurrent beyond
+ * 4095) decided what.  Totals since the context was created, summed on the host after every launch (no device work
+ * here): out[0] decisions kept from a group's speculation, [1] decisions decided alone (the two owgs_read_stats also
+ * reports, below); then out[0] split by branch: [2] plain (maxConcurrent == 1) and [3] concurrent decisions kept
+ * inside a run committed at once, [4] plain and [5] concurrent decisions kept one at a time in queue order, [6]
+ * speculated walks that fail everywhere and were forced (SCPB:417-424) -- [0] == [2] + ... + [6]; [7] decisions that
+ * had a speculation but were decided alone (it no longer held at their turn, or an earlier decision of their action
+ * / key was decided alone; counted in [1] too); [8] None outcomes of an empty pool (SCPB:288-290) and [9]
+ * IndexOutOfBounds outcomes (SCPB:266-268), counted in neither [0] nor [1] -- every publish is in exactly one of
+ * [2..6], [1], [8], [9]; [10] groups of up to 64 releases whose plain releases were applied at once, [11] groups
+ * applied in queue order (a permit count could leave the int range, FS:48-50); [12] launches of the engine, [13]
+ * launches that stopped for the NestedSemaphore map to grow and were resumed.  Returns the number of counters (14),
+ * or 0 with nothing written while the context runs on the on-chip engines. */
+int owgs_large_stats(owgs_ctx* ctx, int64_t* out, int32_t cap);
+
 /* Restore the slot state captured by owgs_snapshot (bench: every timed step starts from the same state). */
 int owgs_snapshot(owgs_ctx* ctx);
 int owgs_restore(owgs_ctx* ctx, void* stream);
@@ -397,7 +412,9 @@ int owgs_selftest(owgs_ctx* ctx);
 /* Engine counters of the last engine launch (diagnostics): [0] resolution passes, [1] walk probes, [2] overload
  * fallbacks, [3] wave-cooperative long walks, [4] chunks, [5] passes that stopped before the chunk end,
  * [31] lanes re-decided inside their pass; [8..15] per-phase shader cycles in the diagnostic build
- * (libowgs_prof.so). */
+ * (libowgs_prof.so).  On a context that runs on the large-state engine the slots [40..43] (cycles of its releases,
+ * group speculation, kept decisions, decisions decided alone) and [46], [47] (decisions kept from the speculation /
+ * decided alone) are not the last launch's: they are totals since the context was created (owgs_large_stats). */
 int owgs_read_stats(owgs_ctx* ctx, uint64_t* out, int32_t cap);
 
 #ifdef __cplusplus

@@ -72,6 +72,8 @@ _RES_PROF = ("walk_rounds", "decisions", "stage_cycles", "release_cycles", "publ
              "alone_cycles", "speculation_cycles", "validation_cycles", "match_cycles", "plain_walk_cycles",
              "conc_walk_cycles", "insert_cycles", "conc_release_cycles", "prespec_chunks", "helper_cycles")
 _NRP = len(_RES_PROF)
+_LARGE_STATS = ("large_spec", "alone", "run_plain", "run_conc", "kept_plain", "kept_conc", "forced_spec", "rejected",
+                "none_kind", "throw_kind", "rel_groups_par", "rel_groups_ordered", "launches", "resumes")
 
 
 class GpuShardingContainerPoolBalancer:
@@ -243,6 +245,13 @@ class GpuShardingContainerPoolBalancer:
         d["life_exits"] = int(out[11 + 2 * _NRP])  # launches ended by the lifetime bound (OWGS_RES_LIFE_US)
         d["watch_calls"] = int(out[12 + 2 * _NRP])  # served calls while watched pairs existed
         return d
+
+    def large_stats(self) -> dict | None:
+        """owgs_large_stats: which path of the large-state engine decided what, totals since the context was created
+        (`large_spec` == run_plain + run_conc + kept_plain + kept_conc + forced_spec); None on the on-chip engines."""
+        out = np.zeros(len(_LARGE_STATS), np.int64)
+        n = self._chk(self._L.owgs_large_stats(self._h, _p(out), len(out)))
+        return dict(zip(_LARGE_STATS, (int(x) for x in out))) if n else None
 
     def map_fill(self) -> dict:
         """The NestedSemaphore map's fill: live / deleted primary (LDS-image) entries, overflow entries and capacity."""

@@ -342,6 +342,8 @@ struct owgs_ctx {
     DevBuf<uint4> q_cur;   // walk cursors of the large-state engine, per action {generation, step, position, 0}
     uint32_t q_gen = 1;    // the next call's first generation: cursors never outlive the call that wrote them
     int64_t q_spec = 0, q_alone = 0;  // its decisions: kept from the group speculation / decided alone
+    int64_t q_path[OWGS_SEQ_NPATH] = {};  // ... by path (the kernel's state[16..], owgs_large_stats' [2..11])
+    int64_t q_launches = 0, q_resumes = 0;  // its launches / those that stopped for the map to grow
     uint64_t q_cyc[4] = {0, 0, 0, 0};  // its cycles: releases, group speculation, kept decisions, decided alone
     DevBuf<uint32_t> d_hwords;
     const uint32_t* grp_hwords = nullptr;
@@ -1504,7 +1506,7 @@ static OwgsSeqArgs seq_args(owgs_ctx* c) {
 
 // the map keeps `room` more entries under half its capacity: read its fill, grow (rehash live entries) if needed
 static int seq_reserve(owgs_ctx* c, int64_t room, hipStream_t s) {
-    HIPCHK(c, c->q_state.reserve(16));
+    HIPCHK(c, c->q_state.reserve(OWGS_SEQ_NSTATE));
     if (!c->q_filled.p) {
         HIPCHK(c, c->q_filled.reserve(1));
         HIPCHK(c, hipMemsetAsync(c->q_filled.p, 0, 4, s));
@@ -1593,11 +1595,14 @@ static int seq_run(owgs_ctx* c, const OwgsSeqArgs& S0, hipStream_t s) {
         S.state = c->q_state.p;
         S.resume = resume;
         HIPCHK(c, owgs_launch_seq(&S, s));
-        int32_t st[16] = {0};
+        int32_t st[OWGS_SEQ_NSTATE] = {0};
         HIPCHK(c, hipMemcpyAsync(st, c->q_state.p, sizeof(st), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         c->q_spec += st[6];  // (decisions the launch kept from its speculation / decided alone)
         c->q_alone += st[7];
+        for (int k = 0; k < OWGS_SEQ_NPATH; ++k) c->q_path[k] += st[16 + k];
+        ++c->q_launches;
+        c->q_resumes += st[0] == 1 ? 1 : 0;
         for (int k = 0; k < 4; ++k) c->q_cyc[k] += (uint64_t)(uint32_t)st[8 + 2 * k] | ((uint64_t)(uint32_t)st[9 + 2 * k] << 32);
         gen = (uint32_t)st[5];  // (a resumed launch continues the generation it stopped in)
         if (st[0] == 0) break;
@@ -4202,6 +4207,18 @@ int owgs_resident_stats(owgs_ctx* c, int64_t* out, int32_t cap) {
     if (cap > 11 + 2 * OWGS_RES_NPROF) out[11 + 2 * OWGS_RES_NPROF] = c->res_n_life;
     if (cap > 12 + 2 * OWGS_RES_NPROF) out[12 + 2 * OWGS_RES_NPROF] = c->res_n_watch_calls;
     return 13 + 2 * OWGS_RES_NPROF;
+}
+
+int owgs_large_stats(owgs_ctx* c, int64_t* out, int32_t cap) {
+    if (!c || cap < 0 || (cap > 0 && !out)) return OWGS_EINVAL;
+    if (!c->large) return 0;
+    // (host-side totals: every launch of the large-state engine is waited for and summed in seq_run)
+    int64_t v[4 + OWGS_SEQ_NPATH] = {c->q_spec, c->q_alone};
+    for (int k = 0; k < OWGS_SEQ_NPATH; ++k) v[2 + k] = c->q_path[k];
+    v[2 + OWGS_SEQ_NPATH] = c->q_launches;
+    v[3 + OWGS_SEQ_NPATH] = c->q_resumes;
+    for (int32_t i = 0; i < cap && i < 4 + OWGS_SEQ_NPATH; ++i) out[i] = v[i];
+    return 4 + OWGS_SEQ_NPATH;
 }
 
 int owgs_engine_ms(owgs_ctx* c, float* ms) {

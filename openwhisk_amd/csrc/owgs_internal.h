@@ -420,6 +420,8 @@ struct OwgsResArgs {
 // Large-state engine (owgs_seq.hip): contexts beyond the on-chip image (owgs_limits) or with maxConcurrent beyond
 // OWGS_MAX_CONC.  Permits in HBM, one HBM map keyed by the full (invoker, fqn@version) pair, 32-bit walk positions.
 #define OWGS_SEQ_MAX_WORDS 16383  // usable-bitmap words of the large-state engine (524,256 invoker ids; pools up to 524,287 positions, owgs_coprime_max)
+#define OWGS_SEQ_NPATH 10   // path counters of one launch of the large-state engine (owgs_seq.hip), state[16..]
+#define OWGS_SEQ_NSTATE (16 + OWGS_SEQ_NPATH)
 struct OwgsSeqArgs {
     int32_t* permits;
     int32_t n_slots;
@@ -459,7 +461,9 @@ struct OwgsSeqArgs {
     int32_t* out_inv;
     uint8_t* out_flags;
     unsigned long long rng_seed;
-    int32_t* state;               // [5] {stopped for a map growth, run, phase, index lo, hi} -- resumed when resume != 0
+    int32_t* state;               // [OWGS_SEQ_NSTATE] {stopped for a map growth, run, phase, index lo, hi} -- resumed
+                                  //   when resume != 0; [5] generation, [6..7] decisions kept / alone, [8..15]
+                                  //   cycles, [16..] the launch's path counters (OWGS_SEQ_NPATH, owgs_large_stats)
     int32_t resume;
     int32_t* err;
 };

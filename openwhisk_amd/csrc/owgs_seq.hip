@@ -209,6 +209,11 @@ __global__ __launch_bounds__(64) void owgs_seq_kernel(OwgsSeqArgs S) {
     long long j = S.resume ? ((long long)(uint32_t)S.state[3] | ((long long)S.state[4] << 32)) : -1;
     bool stop = false;
     int n_spec = 0, n_alone = 0;  // decisions kept from the speculation / decided alone (state[6], state[7])
+    // ... by path (state[16..25], owgs_large_stats; wave-uniform): kept inside a fast run (plain, concurrent), kept in
+    // order (plain, concurrent), a speculated failed walk forced, speculated but decided alone, the None and
+    // IndexOutOfBounds outcomes, release groups applied in parallel / in queue order
+    int n_run_p = 0, n_run_c = 0, n_kept_p = 0, n_kept_c = 0, n_forced = 0, n_rej = 0, n_none = 0, n_throw = 0;
+    int n_rel_par = 0, n_rel_ord = 0;
     // cycles (s_memtime) by phase, state[8..15] as 4 x u64: releases, a group's gather + ranks + speculation, its
     // decisions kept from the speculation, its decisions decided alone
     u64 cy0 = 0, cy1 = 0, cy2 = 0, cy3 = 0;
@@ -263,6 +268,8 @@ __global__ __launch_bounds__(64) void owgs_seq_kernel(OwgsSeqArgs S) {
                 const long long g_room = (long long)wave_sum(g_in ? g_mem : 0);
                 const bool par = __ballot(g_in && (long long)g_p + g_room > 0x7FFFFFFFll) == 0ull;
                 const bool g_plain = par && g_in && g_maxc <= 1;
+                n_rel_par += par ? 1 : 0;
+                n_rel_ord += par ? 0 : 1;
                 if (g_plain) atomicAdd(&S.permits[g_inv], g_mem);
                 if (__ballot(g_plain)) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                 int my_f = 0;
@@ -661,6 +668,8 @@ __global__ __launch_bounds__(64) void owgs_seq_kernel(OwgsSeqArgs S) {
                             }
                         }
                         n_spec += L - q;
+                        n_run_p += __popcll(__ballot(fast && fp));
+                        n_run_c += __popcll(__ballot(fast && fc));
                         q = L;
                         tick(2);
                         if (q >= nq) break;
@@ -699,6 +708,7 @@ __global__ __launch_bounds__(64) void owgs_seq_kernel(OwgsSeqArgs S) {
                         taken_at = t;
                         taken = mem;
                         spec_done = true;
+                        ++n_kept_p;
                         kept_plain = qu;
                         if (S.cur) {
                             const int aq = __builtin_amdgcn_readlane(g_a, q);
@@ -738,10 +748,12 @@ __global__ __launch_bounds__(64) void owgs_seq_kernel(OwgsSeqArgs S) {
                         taken_at = t;
                         taken = c0 >= 1 ? 0 : mem;
                         spec_done = true;
+                        ++n_kept_c;
                     }
                 } else if (kind == 0 && qk == 2 && !qinv) {  // the walk fails everywhere: forced (SCPB:417-424)
                     const int H = pool ? hb : hm;
                     spec_done = true;
+                    ++n_forced;
                     if (H > 0) {
                         const int t = select_usable(base, (int)rng_index(S.rng_seed, seq, (uint32_t)H));
                         if (t < 0) err = 1;
@@ -768,12 +780,15 @@ __global__ __launch_bounds__(64) void owgs_seq_kernel(OwgsSeqArgs S) {
                     ++n_spec;
                 } else if (kind == 1) {
                     out = OWGS_NONE_V;  // no invokers in the pool: None (SCPB:288-290)
+                    ++n_none;
                 } else if (kind == 2) {
                     out = OWGS_THROW_V;  // Int.MinValue hash: stepSizes / invokers index out of bounds (SCPB:266-268)
+                    ++n_throw;
                 } else {
                     flush();
                     mem_done();  // (the stores of this group's speculated decisions, before this walk reads the state)
                     ++n_alone;
+                    n_rej += qk != 0 ? 1 : 0;  // (its speculation did not hold, or an earlier one's of its action / key)
                     const uint32_t step = (uint32_t)__builtin_amdgcn_readlane((int)g_step, q);
                     int t = -1;
                     // probes s = s0 + 64 u + lane, u = 0..3, in walk order (u, then lane); position (home + s step) mod
@@ -972,6 +987,10 @@ __global__ __launch_bounds__(64) void owgs_seq_kernel(OwgsSeqArgs S) {
             S.state[8 + 2 * k] = (int)(uint32_t)cys[k];
             S.state[9 + 2 * k] = (int)(uint32_t)(cys[k] >> 32);
         }
+        const int paths[OWGS_SEQ_NPATH] = {n_run_p, n_run_c, n_kept_p, n_kept_c, n_forced,
+                                           n_rej,   n_none,  n_throw,  n_rel_par, n_rel_ord};
+#pragma unroll
+        for (int k = 0; k < OWGS_SEQ_NPATH; ++k) S.state[16 + k] = paths[k];
         if (any_err) atomicOr(S.err, OWGS_ERR_INTERNAL);
     }
 }

@@ -852,6 +852,8 @@ def test_large_pool_40k_invokers_stream_matches_oracle():
     assert len(w.inv_ids) > mx.value and w.stream.n_batches > 3 and len(w.stream.rel_aid) > 10_000
     b, g_inv, g_fl = check_stream(w)
     assert (g_fl & 1).sum() >= 0 and (g_inv >= 0).all()
+    ls = b.large_stats()  # both kinds of decision were made: kept from a group's speculation, and decided alone
+    assert ls is not None and ls["large_spec"] > 0 and ls["alone"] > 0, ls
 
 
 def test_large_pool_100k_invokers_beyond_the_old_step_kernel_range():
@@ -942,3 +944,5 @@ def test_maxconcurrent_beyond_4095_and_growth_into_the_large_engine():
     for _ in range(10):
         call(400, 200)
     assert np.array_equal(g.permits(), o.permits())
+    ls = g.large_stats()  # the calls since the move: decisions kept from a group's speculation, and decided alone
+    assert ls is not None and ls["large_spec"] > 0 and ls["alone"] > 0, ls
