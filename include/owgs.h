@@ -284,6 +284,48 @@ int owgs_complete_activations(owgs_ctx* ctx, int32_t n, const char* aid32, const
 /* activationSlots.size */
 int owgs_activations_live(owgs_ctx* ctx, int64_t* live);
 
+/* ---- in-flight books (CLB:62-65) ----
+ * totalActivations, totalBlackBoxActivationMemory, totalManagedActivationMemory and activationsPerNamespace, which
+ * setupActivation increments (CLB:121-127) and processCompletion decrements for the entry it removed (CLB:280-284).
+ * They are what LoadBalancer.activeActivationsFor / totalActiveActivations return (CLB:83-85), what the in-flight
+ * gauges emit (CLB:68-79) and what ActivationThrottler.check reads.  The track and completion calls above keep them:
+ *   - tracking counts EVERY item, an id that already has an entry included (CLB:121-127 run before getOrElseUpdate,
+ *     CLB:148): total += 1, the memory total of the action's pool += its megabytes, the item's namespace += 1.  A
+ *     duplicate id so leaks one count, as in the reference.  The entry keeps the namespace and action of its first
+ *     tracker in array order.  A batch rejected with an error counts nothing.
+ *   - a completion whose outcome is OWGS_ACK_RELEASED subtracts the removed ENTRY's values (its action's megabytes
+ *     and pool, its namespace), not the message's.  No other outcome touches a counter.
+ * Per-namespace counters are int32 with wrapping arithmetic (LongAdder.intValue, CLB:84), the totals int64.
+ * owgs_snapshot / owgs_restore leave them alone, as they leave activationSlots alone. */
+
+#define OWGS_NS_INITIAL_CAP 1024 /* namespaces the device counter array holds before its first growth */
+/* msg.user.namespace.uuid (CLB:127, 157) -> dense handle.  uuid128 = 2n words (hi, lo).  Idempotent: a uuid already
+ * registered returns its handle.  Handles are never reused in this version. */
+int owgs_register_namespaces(owgs_ctx* ctx, int32_t n, const uint64_t* uuid128, int32_t* out_ns);
+
+/* owgs_track_activations with msg.user.namespace.uuid per item: ns[i] is a namespace handle or OWGS_NONE (the item
+ * moves the totals and no namespace).  An unknown handle returns OWGS_ENOENT before any state changes.  Outputs and
+ * table behaviour are those of owgs_track_activations, which behaves as ns = OWGS_NONE for every item. */
+int owgs_track_activations_ns(owgs_ctx* ctx, int32_t n, const char* aid32, const int32_t* action, const int32_t* ns,
+                              const int32_t* ticket, int32_t* out_ticket, uint8_t* out_existed);
+
+/* Replaces: activeActivationsFor(namespace) (CLB:83-84) for n namespace handles; ordered after earlier calls. */
+int owgs_active_activations(owgs_ctx* ctx, int32_t n, const int32_t* ns, int32_t* out);
+/* out[0] totalActivations, out[1] totalManagedActivationMemory (MB), out[2] totalBlackBoxActivationMemory (MB)
+ * (CLB:63-65); totalActiveActivations (CLB:85) is (int32_t)out[0].  Ordered after earlier calls. */
+int owgs_activation_totals(owgs_ctx* ctx, int64_t out[3]);
+
+/* Sequential replay, in array order, of ActivationThrottler.check (ActivationThrottler.scala:41-49, ConcurrentRateLimit
+ * :58-59) followed, for admitted jobs, by setupActivation's namespace count (CLB:127):
+ *   count_i = active[ns_i] + #{ j < i : ns_j == ns_i and ok_j };   ok_i = count_i < limit_i
+ * Read-only: no counter changes (they move when the admitted jobs are tracked).
+ * Assumption: an admitted job is tracked afterwards.  That holds whenever the pool has a usable invoker: schedule
+ * returns None only with no healthy invoker (SCPB:398-436), and only then does publish skip setupActivation; a batch
+ * checked while no invoker is usable counts admitted jobs that will not be tracked against the later jobs of their
+ * namespace.  ns[i] = OWGS_NONE returns OWGS_EINVAL, an unknown handle OWGS_ENOENT. */
+int owgs_throttle_batch(owgs_ctx* ctx, int32_t n, const int32_t* ns, const int32_t* limit, int32_t* out_count,
+                        uint8_t* out_ok);
+
 /* ---- invoker health supervision ----
  * Replaces: InvokerPool (InvokerSupervision.scala:95-210: registerInvoker on the first ping, padToIndexed with Offline
  * entries, InvocationFinishedMessage forwarding) and one InvokerActor FSM per invoker (InvokerSupervision.scala:

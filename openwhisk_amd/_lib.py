@@ -22,6 +22,7 @@ FLAG_OVERLOAD = 1
 REL_NOSUCHELEMENT, REL_OVERFLOW, REL_NOENTRY = 1, 2, 4
 ACK_FAIL, ACK_JVM, ACK_UNSUPPORTED, ACK_RELEASED, ACK_HEALTH, ACK_NOENTRY, ACK_FORCED_NOENTRY = range(7)
 HEALTHY, UNHEALTHY, UNRESPONSIVE, OFFLINE = 0, 1, 2, 3
+NS_INITIAL_CAP = 1024  # OWGS_NS_INITIAL_CAP: namespaces the device counter array holds before it first grows
 
 
 class OwgsError(RuntimeError):
@@ -125,6 +126,11 @@ def lib() -> C.CDLL:
         "owgs_process_acks_device": (C.c_int, [P, i32, P, P, P, P, P, P, P]),
         "owgs_complete_activations": (C.c_int, [P, i32, P, P, P, P, P, P]),
         "owgs_activations_live": (C.c_int, [P, P]),
+        "owgs_register_namespaces": (C.c_int, [P, i32, P, P]),
+        "owgs_track_activations_ns": (C.c_int, [P, i32, P, P, P, P, P, P]),
+        "owgs_active_activations": (C.c_int, [P, i32, P, P]),
+        "owgs_activation_totals": (C.c_int, [P, P]),
+        "owgs_throttle_batch": (C.c_int, [P, i32, P, P, P, P]),
         "owgs_replay_device": (C.c_int, [P, i32, P, P, C.c_int64, P, P, C.c_int64, u64, P, P, P, P]),
         "owgs_replay_device_multi": (C.c_int, [P, i32, P, P]),
         "owgs_replay_device_span": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P, u64, P, P, P, P]),

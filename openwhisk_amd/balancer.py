@@ -282,16 +282,65 @@ class GpuShardingContainerPoolBalancer:
         """TransactionId.invokerHealth's start time (TransactionId.scala:225): health acks echo it."""
         self._chk(self._L.owgs_set_health_tid(self._h, start_ms))
 
-    def track_activations(self, aids, actions, tickets):
-        """setupActivation's activationSlots.getOrElseUpdate (CLB:148-166) for a batch: (ticket, existed)."""
+    def track_activations(self, aids, actions, tickets, *, ns=None):
+        """setupActivation's activationSlots.getOrElseUpdate (CLB:148-166) for a batch: (ticket, existed).  Every item
+        also counts into the in-flight books (CLB:121-127), duplicates included; `ns` = namespace handles
+        (register_namespaces; NONE for an item without one) moves activationsPerNamespace too."""
         n = len(aids)
         buf = np.frombuffer(b"".join(a.encode("ascii") for a in aids) or b"\0", dtype=np.uint8)
         act = np.ascontiguousarray(actions, dtype=np.int32)
         tk = np.ascontiguousarray(tickets, dtype=np.int32)
         out = np.zeros(max(n, 1), dtype=np.int32)
         ex = np.zeros(max(n, 1), dtype=np.uint8)
-        self._chk(self._L.owgs_track_activations(self._h, n, _p(buf), _p(act), _p(tk), _p(out), _p(ex)))
+        if ns is None:
+            self._chk(self._L.owgs_track_activations(self._h, n, _p(buf), _p(act), _p(tk), _p(out), _p(ex)))
+        else:
+            h = np.ascontiguousarray(ns, dtype=np.int32)
+            if len(h) != n:
+                raise ValueError("ns needs one handle per activation")
+            h = h if n else np.zeros(1, np.int32)
+            self._chk(self._L.owgs_track_activations_ns(self._h, n, _p(buf), _p(act), _p(h), _p(tk), _p(out), _p(ex)))
         return out[:n], ex[:n]
+
+    def register_namespaces(self, uuids) -> np.ndarray:
+        """msg.user.namespace.uuid -> dense namespace handles (idempotent).  uuids: 128-bit ints, uuid.UUID values or
+        32-hex-digit strings."""
+        vals = [u.int if hasattr(u, "int") else int(u, 16) if isinstance(u, str) else int(u) for u in uuids]
+        n = len(vals)
+        w = np.zeros(max(2 * n, 2), dtype=np.uint64)
+        w[0:2 * n:2] = [v >> 64 for v in vals]
+        w[1:2 * n:2] = [v & (2**64 - 1) for v in vals]
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._L.owgs_register_namespaces(self._h, n, _p(w), _p(out)))
+        return out[:n]
+
+    def active_activations_for(self, ns) -> np.ndarray:
+        """activeActivationsFor (CLB:83-84) for namespace handles."""
+        h = np.ascontiguousarray(ns, dtype=np.int32)
+        n = len(h)
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._L.owgs_active_activations(self._h, n, _p(h if n else np.zeros(1, np.int32)), _p(out)))
+        return out[:n]
+
+    def activation_totals(self) -> tuple[int, int, int]:
+        """(totalActivations, totalManagedActivationMemory MB, totalBlackBoxActivationMemory MB) (CLB:63-65)."""
+        out = np.zeros(3, dtype=np.int64)
+        self._chk(self._L.owgs_activation_totals(self._h, _p(out)))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def throttle_batch(self, ns, limits) -> tuple[np.ndarray, np.ndarray]:
+        """ActivationThrottler.check replayed in array order over a drained batch (owgs_throttle_batch):
+        (count, ok) per job; an admitted job counts against the later jobs of its namespace."""
+        h = np.ascontiguousarray(ns, dtype=np.int32)
+        lim = np.ascontiguousarray(limits, dtype=np.int32)
+        n = len(h)
+        if len(lim) != n:
+            raise ValueError("limits needs one value per job")
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        ok = np.zeros(max(n, 1), dtype=np.uint8)
+        z = np.zeros(1, np.int32)
+        self._chk(self._L.owgs_throttle_batch(self._h, n, _p(h if n else z), _p(lim if n else z), _p(cnt), _p(ok)))
+        return cnt[:n], ok[:n]
 
     def process_acks(self, msgs):
         """processAcknowledgement (CLB:205-232) for raw ack messages (bytes): (kind, invoker, ticket, flags)."""

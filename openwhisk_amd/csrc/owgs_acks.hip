@@ -22,6 +22,9 @@
 //   owgs_ack_resolve_kernel  processCompletion outcome per message + the release record of releaseInvoker
 //                            (SCPB:327-331: invokerSlots.lift(invoker.toInt) -- out-of-range ids are no-ops),
 //                            applied in message order by owgs_release_seq_kernel (owgs_kernels.hip).
+// The fill and resolve kernels also keep the controller's in-flight books (totalActivations, the two memory totals,
+// activationsPerNamespace: CLB:62-65), incremented at CLB:121-127 and decremented at CLB:280-284; see "in-flight
+// books" below.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -502,6 +505,47 @@ __device__ __forceinline__ bool keq(ulonglong2 a, ulonglong2 b) { return a.x == 
 #define TW_TOMB 2ull
 #define TW_CLAIM (1ull << 63)
 
+// ------------------------------------------------------------------------------------------ in-flight books
+// activationsPerNamespace(h) += delta (CLB:127 / CLB:283) for every lane whose h is a namespace handle; every lane of
+// the wave calls it (lanes without an item pass OWGS_NONE_V).
+// Wave-level aggregation: the lanes holding one handle elect their lowest lane, which adds the group's size (a hot
+// namespace takes a large share of a batch: one atomic per wave on its word instead of one per item).  The plain
+// form, one no-return atomic per lane, was measured beside it and dropped: on 50,000 ids of the headline draw (1,000
+// namespaces, the hottest 10 % of the batch) it cost the completion call 48 us against 5 us.
+__device__ __forceinline__ void ns_count(int32_t* active, int h, int delta) {
+    const int lane = (int)(threadIdx.x & 63);
+    u64 todo = __ballot(h != OWGS_NONE_V);
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int hl = __shfl(h, leader);
+        const u64 grp = __ballot(h == hl);
+        if (lane == leader) atomicAdd(&active[hl], delta * __popcll(grp));
+        todo &= ~grp;
+    }
+}
+
+// the call's memory words: megabytes of the items it counted, managed and blackbox (CLB:123-125 / CLB:281-283), as a
+// block reduction and one atomic per block and word; every thread of the block calls it (mb = 0 without an item)
+__device__ __forceinline__ void mb_totals_add(unsigned long long* counters, int mb, bool bb) {
+    __shared__ u64 red[2][4];
+    u64 m = bb ? 0ull : (u64)(long long)mb, b = bb ? (u64)(long long)mb : 0ull;
+    for (int o = 32; o; o >>= 1) {
+        m += __shfl_xor(m, o);
+        b += __shfl_xor(b, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = m;
+        red[1][threadIdx.x >> 6] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        b = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        if (m) atomicAdd(&counters[OWGS_CNT_MANAGED_MB], m);
+        if (b) atomicAdd(&counters[OWGS_CNT_BLACKBOX_MB], b);
+    }
+}
+
 // track step 1: find or claim a slot for every id of the batch
 __global__ __launch_bounds__(256) void owgs_act_claim_kernel(OwgsActTable T, const ulonglong2* key, int32_t n,
                                                              const uint8_t* info, int32_t* slot, uint8_t* state) {
@@ -548,36 +592,49 @@ __global__ __launch_bounds__(256) void owgs_act_claim_kernel(OwgsActTable T, con
     state[i] = 3;
 }
 
-// track step 2: the lowest batch index of each claimed slot writes the entry (getOrElseUpdate in array order)
+// track step 2: the lowest batch index of each claimed slot writes the entry (getOrElseUpdate in array order), its
+// namespace included: the entry keeps the namespace and action of its first tracker (CLB:148-166).
+// Every item is counted, duplicates too: setupActivation increments totalActivations, the memory total of the action's
+// pool and activationsPerNamespace (CLB:121-127) BEFORE activationSlots.getOrElseUpdate (CLB:148), so an id that
+// already has an entry leaks one count in the reference -- and here.  (totalActivations += n is the host's.)
 __global__ __launch_bounds__(256) void owgs_act_fill_kernel(OwgsActTable T, const ulonglong2* key, int32_t n,
-                                                            const int32_t* action, const int32_t* ticket,
-                                                            const int32_t* slot, const uint8_t* state,
-                                                            int32_t* out_ticket, uint8_t* out_existed,
-                                                            unsigned long long* counters) {
+                                                            const int32_t* action, const int32_t* ns,
+                                                            const int32_t* ticket, const int32_t* slot,
+                                                            const uint8_t* state, int32_t* out_ticket,
+                                                            uint8_t* out_existed, unsigned long long* counters,
+                                                            OwgsInflight F) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int s = slot[i];
-    if (s < 0) {
-        out_existed[i] = 2;
-        out_ticket[i] = -1;
-        return;
+    int h = OWGS_NONE_V, mb = 0;
+    bool bb = false;
+    if (i < n) {
+        const int a = action[i];
+        h = ns ? ns[i] : OWGS_NONE_V;  // msg.user.namespace.uuid's handle (CLB:127)
+        mb = F.act_mem[a];           // action.limits.memory.megabytes (CLB:125)
+        bb = F.act_bb[a] != 0;       // action.exec.pull (CLB:122)
+        const int s = slot[i];
+        if (s < 0) {
+            out_existed[i] = 2;
+            out_ticket[i] = -1;
+        } else if (state[i] == 1) {
+            out_existed[i] = 1;
+            out_ticket[i] = T.tv[s].y;
+        } else {
+            const int o = T.owner[s];
+            if (o == i) {
+                T.tk[s] = key[i];
+                T.tv[s] = make_int2(a, ticket[i]);
+                T.tn[s] = h;
+                out_existed[i] = 0;
+                out_ticket[i] = ticket[i];
+                atomicAdd(&counters[OWGS_CNT_INSERTED], 1ull);
+            } else {
+                out_existed[i] = 1;
+                out_ticket[i] = ticket[o];
+            }
+        }
     }
-    if (state[i] == 1) {
-        out_existed[i] = 1;
-        out_ticket[i] = T.tv[s].y;
-        return;
-    }
-    const int o = T.owner[s];
-    if (o == i) {
-        T.tk[s] = key[i];
-        T.tv[s] = make_int2(action[i], ticket[i]);
-        out_existed[i] = 0;
-        out_ticket[i] = ticket[i];
-        atomicAdd(&counters[0], 1ull);
-    } else {
-        out_existed[i] = 1;
-        out_ticket[i] = ticket[o];
-    }
+    ns_count(F.active, h, 1);
+    mb_totals_add(counters, mb, bb);
 }
 
 // track step 3: publish the claimed slots and reset the owner words
@@ -615,42 +672,55 @@ __global__ __launch_bounds__(256) void owgs_act_find_kernel(OwgsActTable T, cons
     slot[i] = r;
 }
 
-// completion step 2: processCompletion outcome + releaseInvoker record (CLB:286-345, SCPB:327-331)
+// completion step 2: processCompletion outcome + releaseInvoker record (CLB:286-345, SCPB:327-331).  A message that
+// removes its entry (OWGS_ACK_RELEASED) also takes the entry out of the in-flight books with the ENTRY's values, not
+// the message's (CLB:280-284: totalActivations.decrement, the memory total of entry.isBlackbox by entry.memoryLimit,
+// activationsPerNamespace.get(entry.namespaceId).foreach(_.decrement())); no other outcome touches a counter.
+// (totalActivations -= entries removed is the host's.)
 __global__ __launch_bounds__(256) void owgs_ack_resolve_kernel(OwgsActTable T, int32_t n, const uint8_t* info,
                                                                const int32_t* inst, const int32_t* slot,
                                                                const int32_t* act_mem, const int32_t* act_maxc,
                                                                const int32_t* act_slot, int32_t n_slots,
                                                                int32_t* r_inv, int32_t* r_mem, int32_t* r_maxc,
                                                                int32_t* r_slot, uint8_t* out_kind,
-                                                               int32_t* out_ticket, unsigned long long* counters) {
+                                                               int32_t* out_ticket, unsigned long long* counters,
+                                                               OwgsInflight F) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int k = info[i] & 7;
-    const int s = slot[i];
-    int outk = k, tk = -1, ri = 0x7FFFFFFF, rm = 1, rc = 1, rs = 0;
-    if (k == OWGS_ACK_COMPLETION) {
-        if (s >= 0 && T.owner[s] == i) {
-            const int2 v = T.tv[s];
-            outk = OWGS_ACK_RELEASED;
-            tk = v.y;
-            const int inv = inst[i];
-            ri = (inv >= 0 && inv < n_slots) ? inv : 0x7FFFFFFF;  // invokerSlots.lift(invoker.toInt)
-            rm = act_mem[v.x];
-            rc = act_maxc[v.x];
-            rs = act_slot[v.x];
-            atomicAdd(&counters[1], 1ull);
-        } else if ((info[i] >> 5) & 1) {
-            outk = OWGS_ACK_HEALTH;  // None if tid == TransactionId.invokerHealth (CLB:320-328)
-        } else {
-            outk = ((info[i] >> 6) & 1) ? OWGS_ACK_FORCED_NOENTRY : OWGS_ACK_NOENTRY;  // CLB:329-345
+    int h = OWGS_NONE_V, mb = 0;
+    bool bb = false;
+    if (i < n) {
+        const int k = info[i] & 7;
+        const int s = slot[i];
+        int outk = k, tk = -1, ri = 0x7FFFFFFF, rm = 1, rc = 1, rs = 0;
+        if (k == OWGS_ACK_COMPLETION) {
+            if (s >= 0 && T.owner[s] == i) {
+                const int2 v = T.tv[s];
+                outk = OWGS_ACK_RELEASED;
+                tk = v.y;
+                const int inv = inst[i];
+                ri = (inv >= 0 && inv < n_slots) ? inv : 0x7FFFFFFF;  // invokerSlots.lift(invoker.toInt)
+                rm = act_mem[v.x];
+                rc = act_maxc[v.x];
+                rs = act_slot[v.x];
+                atomicAdd(&counters[OWGS_CNT_REMOVED], 1ull);
+                h = T.tn[s];               // entry.namespaceId (CLB:283)
+                mb = rm;                   // entry.memoryLimit.toMB (CLB:282)
+                bb = F.act_bb[v.x] != 0;   // entry.isBlackbox (CLB:281)
+            } else if ((info[i] >> 5) & 1) {
+                outk = OWGS_ACK_HEALTH;  // None if tid == TransactionId.invokerHealth (CLB:320-328)
+            } else {
+                outk = ((info[i] >> 6) & 1) ? OWGS_ACK_FORCED_NOENTRY : OWGS_ACK_NOENTRY;  // CLB:329-345
+            }
         }
+        r_inv[i] = ri;
+        r_mem[i] = rm;
+        r_maxc[i] = rc;
+        r_slot[i] = rs;
+        out_kind[i] = (uint8_t)outk;
+        out_ticket[i] = tk;
     }
-    r_inv[i] = ri;
-    r_mem[i] = rm;
-    r_maxc[i] = rc;
-    r_slot[i] = rs;
-    out_kind[i] = (uint8_t)outk;
-    out_ticket[i] = tk;
+    ns_count(F.active, h, -1);
+    mb_totals_add(counters, mb, bb);
 }
 
 // completion step 3: tombstone removed entries, reset owner words
@@ -672,7 +742,7 @@ __global__ __launch_bounds__(256) void owgs_ack_flags_kernel(int32_t n, const ui
     out_flags[i] = (uint8_t)(((info[i] >> 4) & 1) | (rel ? (rflags[i] & 3) << 1 : 0));
 }
 
-// rehash live entries into a fresh table (all keys distinct: plain CAS insertion)
+// rehash live entries into a fresh table (all keys distinct: plain CAS insertion); the namespace travels with the entry
 __global__ __launch_bounds__(256) void owgs_act_rehash_kernel(OwgsActTable O, OwgsActTable T) {
     const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (s >= O.cap || O.tw[s] != TW_READY) return;
@@ -683,6 +753,7 @@ __global__ __launch_bounds__(256) void owgs_act_rehash_kernel(OwgsActTable O, Ow
         if (atomicCAS(&T.tw[t], TW_EMPTY, TW_READY) == TW_EMPTY) {
             T.tk[t] = k;
             T.tv[t] = O.tv[s];
+            T.tn[t] = O.tn[s];
             return;
         }
         t = (t + 1) & mask;
@@ -723,13 +794,13 @@ extern "C" hipError_t owgs_launch_act_rehash(const OwgsActTable* O, const OwgsAc
 }
 
 extern "C" hipError_t owgs_launch_act_track(const OwgsActTable* T, const ulonglong2* key, int32_t n,
-                                            const int32_t* action, const int32_t* ticket, int32_t* slot,
-                                            uint8_t* state, int32_t* out_ticket, uint8_t* out_existed,
-                                            unsigned long long* counters, hipStream_t st) {
+                                            const int32_t* action, const int32_t* ns, const int32_t* ticket,
+                                            int32_t* slot, uint8_t* state, int32_t* out_ticket, uint8_t* out_existed,
+                                            unsigned long long* counters, const OwgsInflight* F, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(owgs_act_claim_kernel, GRID(n), *T, key, n, (const uint8_t*)nullptr, slot, state);
-    hipLaunchKernelGGL(owgs_act_fill_kernel, GRID(n), *T, key, n, action, ticket, slot, state, out_ticket,
-                       out_existed, counters);
+    hipLaunchKernelGGL(owgs_act_fill_kernel, GRID(n), *T, key, n, action, ns, ticket, slot, state, out_ticket,
+                       out_existed, counters, *F);
     hipLaunchKernelGGL(owgs_act_publish_kernel, GRID(n), *T, n, slot, state);
     return hipGetLastError();
 }
@@ -740,7 +811,7 @@ extern "C" hipError_t owgs_launch_ack_complete(const OwgsActTable* T, const Owgs
     hipLaunchKernelGGL(owgs_act_find_kernel, GRID(a->n), *T, a->key, a->n, a->info, a->slot);
     hipLaunchKernelGGL(owgs_ack_resolve_kernel, GRID(a->n), *T, a->n, a->info, a->inst, a->slot, a->act_mem,
                        a->act_maxc, a->act_slot, a->n_slots, a->r_inv, a->r_mem, a->r_maxc, a->r_slot, a->out_kind,
-                       a->out_ticket, a->counters);
+                       a->out_ticket, a->counters, a->fl);
     hipLaunchKernelGGL(owgs_act_remove_kernel, GRID(a->n), *T, a->n, a->slot);
     return hipGetLastError();
 }

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -63,9 +64,16 @@ extern "C" hipError_t owgs_launch_aid_decode(const char* aid32, int32_t n, const
 extern "C" hipError_t owgs_launch_act_init(const OwgsActTable* T, hipStream_t st);
 extern "C" hipError_t owgs_launch_act_rehash(const OwgsActTable* O, const OwgsActTable* T, hipStream_t st);
 extern "C" hipError_t owgs_launch_act_track(const OwgsActTable* T, const ulonglong2* key, int32_t n,
-                                            const int32_t* action, const int32_t* ticket, int32_t* slot,
-                                            uint8_t* state, int32_t* out_ticket, uint8_t* out_existed,
-                                            unsigned long long* counters, hipStream_t st);
+                                            const int32_t* action, const int32_t* ns, const int32_t* ticket,
+                                            int32_t* slot, uint8_t* state, int32_t* out_ticket, uint8_t* out_existed,
+                                            unsigned long long* counters, const OwgsInflight* F, hipStream_t st);
+extern "C" hipError_t owgs_launch_ns_gather(const int32_t* active, const int32_t* ns, int32_t n, int32_t* out,
+                                            hipStream_t st);
+extern "C" size_t owgs_throttle_sort_bytes(int32_t n, int32_t bits);
+extern "C" hipError_t owgs_launch_throttle(const int32_t* ns, const int32_t* limit, int32_t n, int32_t bits,
+                                           void* temp, size_t temp_bytes, int32_t* key_out, int32_t* idx_in,
+                                           int32_t* idx_out, const int32_t* active, int32_t* out_count,
+                                           uint8_t* out_ok, hipStream_t st);
 extern "C" hipError_t owgs_launch_ack_complete(const OwgsActTable* T, const OwgsAckCompleteArgs* a, hipStream_t st);
 extern "C" hipError_t owgs_launch_ack_flags(int32_t n, const uint8_t* info, const uint8_t* rflags,
                                             const uint8_t* out_kind, uint8_t* out_flags, hipStream_t st);
@@ -291,8 +299,16 @@ struct owgs_ctx {
     DevBuf<unsigned long long> t_tw;
     DevBuf<ulonglong2> t_tk;
     DevBuf<int2> t_tv;
-    DevBuf<int32_t> t_owner;
+    DevBuf<int32_t> t_tn, t_owner;
     long long t_cap = 0, t_used = 0, t_live = 0;
+    // the in-flight books (CLB:62-65): namespace uuid -> dense handle, the per-namespace counters on the device
+    // (int32, ns_cap entries, zero beyond the registered handles), the three totals on the host (folded in from each
+    // call's counter words at the synchronisation the call ends with)
+    std::map<std::pair<uint64_t, uint64_t>, int32_t> ns_map;
+    DevBuf<int32_t> d_ns_active, q_key, q_idx0, q_idx1;
+    DevBuf<uint8_t> q_temp;
+    int32_t ns_cap = 0;
+    long long f_total = 0, f_mb_managed = 0, f_mb_blackbox = 0;
     long long health_ms = 0;
     DevBuf<ulonglong2> k_key;
     DevBuf<uint8_t> k_info, k_state, k_kind, k_oflags, k_bytes, k_cfl;
@@ -1831,7 +1847,13 @@ void owgs_destroy(owgs_ctx* c) {
     c->t_tw.release();
     c->t_tk.release();
     c->t_tv.release();
+    c->t_tn.release();
     c->t_owner.release();
+    c->d_ns_active.release();
+    c->q_key.release();
+    c->q_idx0.release();
+    c->q_idx1.release();
+    c->q_temp.release();
     c->k_key.release();
     c->k_info.release();
     c->k_state.release();
@@ -3553,6 +3575,7 @@ static OwgsActTable act_table(owgs_ctx* c) {
     T.tw = c->t_tw.p;
     T.tk = c->t_tk.p;
     T.tv = c->t_tv.p;
+    T.tn = c->t_tn.p;
     T.owner = c->t_owner.p;
     T.cap = c->t_cap;
     return T;
@@ -3568,12 +3591,13 @@ static int act_reserve(owgs_ctx* c, long long n) {
     DevBuf<unsigned long long> tw;
     DevBuf<ulonglong2> tk;
     DevBuf<int2> tv;
-    DevBuf<int32_t> ow;
+    DevBuf<int32_t> tn, ow;
     HIPCHK(c, tw.reserve((size_t)cap));
     HIPCHK(c, tk.reserve((size_t)cap));
     HIPCHK(c, tv.reserve((size_t)cap));
+    HIPCHK(c, tn.reserve((size_t)cap));
     HIPCHK(c, ow.reserve((size_t)cap));
-    OwgsActTable T{tw.p, tk.p, tv.p, ow.p, cap};
+    OwgsActTable T{tw.p, tk.p, tv.p, tn.p, ow.p, cap};
     HIPCHK(c, owgs_launch_act_init(&T, c->stream));
     if (c->t_cap > 0) {
         OwgsActTable O = act_table(c);
@@ -3583,14 +3607,17 @@ static int act_reserve(owgs_ctx* c, long long n) {
     c->t_tw.release();
     c->t_tk.release();
     c->t_tv.release();
+    c->t_tn.release();
     c->t_owner.release();
     c->t_tw = tw;
     c->t_tk = tk;
     c->t_tv = tv;
+    c->t_tn = tn;
     c->t_owner = ow;
     tw.p = nullptr;
     tk.p = nullptr;
     tv.p = nullptr;
+    tn.p = nullptr;
     ow.p = nullptr;
     c->t_cap = cap;
     c->t_used = c->t_live;
@@ -3609,11 +3636,25 @@ int owgs_activations_live(owgs_ctx* c, int64_t* live) {
     return OWGS_OK;
 }
 
-int owgs_track_activations(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* action, const int32_t* ticket,
-                           int32_t* out_ticket, uint8_t* out_existed) {
+static OwgsInflight inflight_args(owgs_ctx* c) {
+    OwgsInflight F;
+    F.active = c->d_ns_active.p;
+    F.act_mem = c->d_act_mem.p;
+    F.act_bb = c->d_act_bb.p;
+    return F;
+}
+
+// ns = null: every item without a namespace (owgs_track_activations)
+static int track_impl(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* action, const int32_t* ns,
+                      const int32_t* ticket, int32_t* out_ticket, uint8_t* out_existed) {
     if (!c || n < 0 || (n > 0 && (!aid32 || !action || !ticket || !out_ticket || !out_existed))) return OWGS_EINVAL;
     if (n == 0) return OWGS_OK;
     if (!registered(c, n, action)) return c->fail(OWGS_ENOENT, "unknown action");
+    if (ns) {
+        const int32_t nn = (int32_t)c->ns_map.size();
+        for (int32_t i = 0; i < n; ++i)
+            if (ns[i] != OWGS_NONE && (ns[i] < 0 || ns[i] >= nn)) return c->fail(OWGS_ENOENT, "unknown namespace");
+    }
     // ActivationId.asString is 32 chars of [0-9a-f]; reject a malformed batch before any entry is created
     for (size_t k = 0; k < (size_t)n * 32; ++k) {
         const char ch = aid32[k];
@@ -3635,22 +3676,46 @@ int owgs_track_activations(owgs_ctx* c, int32_t n, const char* aid32, const int3
     HIPCHK(c, c->k_state.reserve((size_t)n));
     HIPCHK(c, c->k_tick.reserve((size_t)n));
     HIPCHK(c, c->k_oflags.reserve((size_t)n));
-    HIPCHK(c, c->k_cnt.reserve(2));
-    HIPCHK(c, hipMemsetAsync(c->k_cnt.p, 0, 16, c->stream));
+    if (ns) HIPCHK(c, upload(c->k_r1, ns, (size_t)n, c->stream));
+    HIPCHK(c, c->k_cnt.reserve(OWGS_CNT_WORDS));
+    HIPCHK(c, hipMemsetAsync(c->k_cnt.p, 0, OWGS_CNT_WORDS * 8, c->stream));
     HIPCHK(c, owgs_launch_aid_decode(c->k_aid.p, n, nullptr, c->k_key.p, nullptr, nullptr, nullptr, c->stream));
     OwgsActTable T = act_table(c);
-    HIPCHK(c, owgs_launch_act_track(&T, c->k_key.p, n, c->k_act.p, c->k_r0.p, c->k_slot.p, c->k_state.p, c->k_tick.p,
-                                    c->k_oflags.p, c->k_cnt.p, c->stream));
-    unsigned long long cnt[2];
+    const OwgsInflight F = inflight_args(c);
+    HIPCHK(c, owgs_launch_act_track(&T, c->k_key.p, n, c->k_act.p, ns ? c->k_r1.p : nullptr, c->k_r0.p, c->k_slot.p,
+                                    c->k_state.p, c->k_tick.p, c->k_oflags.p, c->k_cnt.p, &F, c->stream));
+    unsigned long long cnt[OWGS_CNT_WORDS];
     HIPCHK(c, hipMemcpyAsync(out_ticket, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(out_existed, c->k_oflags.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cnt, c->k_cnt.p, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt, c->k_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->t_used += (long long)cnt[0];
-    c->t_live += (long long)cnt[0];
+    c->t_used += (long long)cnt[OWGS_CNT_INSERTED];
+    c->t_live += (long long)cnt[OWGS_CNT_INSERTED];
+    // CLB:121-125 for every item of the batch, duplicates included (they run before getOrElseUpdate, CLB:148)
+    c->f_total += n;
+    c->f_mb_managed += (long long)cnt[OWGS_CNT_MANAGED_MB];
+    c->f_mb_blackbox += (long long)cnt[OWGS_CNT_BLACKBOX_MB];
     for (int32_t i = 0; i < n; ++i)
         if (out_existed[i] == 2) return c->fail(OWGS_EINVAL, "activation id is not 32 characters of [0-9a-f]");
     return OWGS_OK;
+}
+
+int owgs_track_activations(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* action, const int32_t* ticket,
+                           int32_t* out_ticket, uint8_t* out_existed) {
+    return track_impl(c, n, aid32, action, nullptr, ticket, out_ticket, out_existed);
+}
+
+int owgs_track_activations_ns(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* action, const int32_t* ns,
+                              const int32_t* ticket, int32_t* out_ticket, uint8_t* out_existed) {
+    if (n > 0 && !ns) return OWGS_EINVAL;
+    return track_impl(c, n, aid32, action, ns, ticket, out_ticket, out_existed);
+}
+
+// the completion's share of the books (CLB:280-284): one decrement per removed entry, the entries' megabytes
+static void inflight_release(owgs_ctx* c, const unsigned long long* cnt) {
+    c->f_total -= (long long)cnt[OWGS_CNT_REMOVED];
+    c->f_mb_managed -= (long long)cnt[OWGS_CNT_MANAGED_MB];
+    c->f_mb_blackbox -= (long long)cnt[OWGS_CNT_BLACKBOX_MB];
 }
 
 // shared tail: info/key/inst of n messages are in k_info/k_key/k_inst; resolve, release in order, flags
@@ -3666,12 +3731,13 @@ static int ack_complete(owgs_ctx* c, int32_t n, uint8_t* d_kind, int32_t* d_tick
     HIPCHK(c, c->k_r2.reserve((size_t)n));
     HIPCHK(c, c->k_r3.reserve((size_t)n));
     HIPCHK(c, c->d_rflags.reserve((size_t)n));
-    HIPCHK(c, c->k_cnt.reserve(2));
-    HIPCHK(c, hipMemsetAsync(c->k_cnt.p, 0, 16, st));
+    HIPCHK(c, c->k_cnt.reserve(OWGS_CNT_WORDS));
+    HIPCHK(c, hipMemsetAsync(c->k_cnt.p, 0, OWGS_CNT_WORDS * 8, st));
     if (!c->d_act_mem.p) {  // no actions registered: every lookup misses, the records are never read
         HIPCHK(c, c->d_act_mem.reserve(1));
         HIPCHK(c, c->d_act_maxc.reserve(1));
         HIPCHK(c, c->d_act_slot.reserve(1));
+        HIPCHK(c, c->d_act_bb.reserve(1));
     }
     OwgsActTable T = act_table(c);
     OwgsAckCompleteArgs a{};
@@ -3691,6 +3757,7 @@ static int ack_complete(owgs_ctx* c, int32_t n, uint8_t* d_kind, int32_t* d_tick
     a.out_kind = d_kind;
     a.out_ticket = d_ticket;
     a.counters = c->k_cnt.p;
+    a.fl = inflight_args(c);
     HIPCHK(c, owgs_launch_ack_complete(&T, &a, st));
     if (c->large) {  // the large-state engine applies the records in message order (owgs_seq.hip)
         const int64_t offs[4] = {0, (int64_t)n, 0, 0};
@@ -3707,10 +3774,11 @@ static int ack_complete(owgs_ctx* c, int32_t n, uint8_t* d_kind, int32_t* d_tick
         int rs = seq_run(c, S, st);
         if (rs) return rs;
         HIPCHK(c, owgs_launch_ack_flags(n, c->k_info.p, c->d_rflags.p, d_kind, d_flags, st));
-        unsigned long long cnt[2];
-        HIPCHK(c, hipMemcpyAsync(cnt, c->k_cnt.p, 16, hipMemcpyDeviceToHost, st));
+        unsigned long long cnt[OWGS_CNT_WORDS];
+        HIPCHK(c, hipMemcpyAsync(cnt, c->k_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
-        c->t_live -= (long long)cnt[1];
+        c->t_live -= (long long)cnt[OWGS_CNT_REMOVED];
+        inflight_release(c, cnt);
         return check_err_word(c);
     }
     OwgsReleaseArgs R{};
@@ -3736,10 +3804,11 @@ static int ack_complete(owgs_ctx* c, int32_t n, uint8_t* d_kind, int32_t* d_tick
     R.w = watch_args(c);
     HIPCHK(c, owgs_launch_release_seq(&R, st));
     HIPCHK(c, owgs_launch_ack_flags(n, c->k_info.p, c->d_rflags.p, d_kind, d_flags, st));
-    unsigned long long cnt[2];
-    HIPCHK(c, hipMemcpyAsync(cnt, c->k_cnt.p, 16, hipMemcpyDeviceToHost, st));
+    unsigned long long cnt[OWGS_CNT_WORDS];
+    HIPCHK(c, hipMemcpyAsync(cnt, c->k_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    c->t_live -= (long long)cnt[1];
+    c->t_live -= (long long)cnt[OWGS_CNT_REMOVED];
+    inflight_release(c, cnt);
     rs = w_refresh(c, st);
     return rs ? rs : check_err_word(c);
 }
@@ -3832,6 +3901,117 @@ int owgs_complete_activations(owgs_ctx* c, int32_t n, const char* aid32, const i
     HIPCHK(c, hipMemcpy(out_kind, c->k_kind.p, (size_t)n, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(out_ticket, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(out_flags, c->k_oflags.p, (size_t)n, hipMemcpyDeviceToHost));
+    return OWGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------ in-flight books
+// activationsPerNamespace (CLB:62) on the device, the three totals (CLB:63-65) on the host; see owgs_acks.hip for the
+// counting and owgs_inflight.hip for the reads and the throttle check.
+int owgs_register_namespaces(owgs_ctx* c, int32_t n, const uint64_t* uuid128, int32_t* out_ns) {
+    if (!c || n < 0 || (n > 0 && (!uuid128 || !out_ns))) return OWGS_EINVAL;
+    if (n == 0) return OWGS_OK;
+    // handles of the call: a uuid already registered (before or earlier in this call) keeps its handle
+    std::map<std::pair<uint64_t, uint64_t>, int32_t> fresh;
+    const int64_t have = (int64_t)c->ns_map.size();
+    for (int32_t i = 0; i < n; ++i) {
+        const std::pair<uint64_t, uint64_t> u(uuid128[2 * (size_t)i], uuid128[2 * (size_t)i + 1]);
+        if (!c->ns_map.count(u) && !fresh.count(u)) {
+            const int32_t h = (int32_t)(have + (int64_t)fresh.size());
+            fresh[u] = h;
+        }
+    }
+    const int64_t need = have + (int64_t)fresh.size();
+    if (need > (1 << 30)) return c->fail(OWGS_ERANGE, "more than 2^30 namespaces");
+    if (need > c->ns_cap) {  // grow geometrically on the context's stream; the old counters are copied, the rest zero
+        OWGS_ENTER(c);
+        {
+            const int ro_ = order_on(c, c->stream);
+            if (ro_) return ro_;
+        }
+        int64_t cap = std::max<int64_t>(c->ns_cap, OWGS_NS_INITIAL_CAP);
+        while (cap < need) cap *= 2;
+        DevBuf<int32_t> nb;
+        HIPCHK(c, nb.reserve((size_t)cap));
+        hipError_t e = hipMemsetAsync(nb.p, 0, (size_t)cap * 4, c->stream);
+        if (e == hipSuccess && c->ns_cap > 0)
+            e = hipMemcpyAsync(nb.p, c->d_ns_active.p, (size_t)c->ns_cap * 4, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (the old array is freed below)
+        if (e != hipSuccess) {
+            nb.release();
+            return c->fail(OWGS_EDEVICE, "namespace counters", e);
+        }
+        c->d_ns_active.release();
+        c->d_ns_active = nb;
+        c->ns_cap = (int32_t)cap;
+    }
+    for (const auto& kv : fresh) c->ns_map[kv.first] = kv.second;
+    for (int32_t i = 0; i < n; ++i)
+        out_ns[i] = c->ns_map[std::make_pair(uuid128[2 * (size_t)i], uuid128[2 * (size_t)i + 1])];
+    return OWGS_OK;
+}
+
+static bool ns_known(const owgs_ctx* c, int32_t n, const int32_t* ns) {
+    const int32_t nn = (int32_t)c->ns_map.size();
+    for (int32_t i = 0; i < n; ++i)
+        if (ns[i] < 0 || ns[i] >= nn) return false;
+    return true;
+}
+
+int owgs_active_activations(owgs_ctx* c, int32_t n, const int32_t* ns, int32_t* out) {
+    if (!c || n < 0 || (n > 0 && (!ns || !out))) return OWGS_EINVAL;
+    if (n == 0) return OWGS_OK;
+    if (!ns_known(c, n, ns)) return c->fail(OWGS_ENOENT, "unknown namespace");
+    OWGS_ENTER(c);
+    {
+        const int ro_ = order_on(c, c->stream);
+        if (ro_) return ro_;
+    }
+    HIPCHK(c, upload(c->k_act, ns, (size_t)n, c->stream));
+    HIPCHK(c, c->k_tick.reserve((size_t)n));
+    HIPCHK(c, owgs_launch_ns_gather(c->d_ns_active.p, c->k_act.p, n, c->k_tick.p, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return OWGS_OK;
+}
+
+// (every call that moves the totals ends with a synchronisation and folds its words in there: the host values are
+// ordered after all earlier calls)
+int owgs_activation_totals(owgs_ctx* c, int64_t out[3]) {
+    if (!c || !out) return OWGS_EINVAL;
+    out[0] = c->f_total;
+    out[1] = c->f_mb_managed;
+    out[2] = c->f_mb_blackbox;
+    return OWGS_OK;
+}
+
+int owgs_throttle_batch(owgs_ctx* c, int32_t n, const int32_t* ns, const int32_t* limit, int32_t* out_count,
+                        uint8_t* out_ok) {
+    if (!c || n < 0 || (n > 0 && (!ns || !limit || !out_count || !out_ok))) return OWGS_EINVAL;
+    if (n == 0) return OWGS_OK;
+    for (int32_t i = 0; i < n; ++i)
+        if (ns[i] == OWGS_NONE) return c->fail(OWGS_EINVAL, "throttle check without a namespace");
+    if (!ns_known(c, n, ns)) return c->fail(OWGS_ENOENT, "unknown namespace");
+    OWGS_ENTER(c);
+    {
+        const int ro_ = order_on(c, c->stream);
+        if (ro_) return ro_;
+    }
+    int32_t bits = 1;
+    while (((int64_t)1 << bits) < (int64_t)c->ns_map.size()) ++bits;
+    const size_t tb = owgs_throttle_sort_bytes(n, bits);
+    HIPCHK(c, c->q_temp.reserve(tb));
+    HIPCHK(c, c->q_key.reserve((size_t)n));
+    HIPCHK(c, c->q_idx0.reserve((size_t)n));
+    HIPCHK(c, c->q_idx1.reserve((size_t)n));
+    HIPCHK(c, upload(c->k_act, ns, (size_t)n, c->stream));
+    HIPCHK(c, upload(c->k_r0, limit, (size_t)n, c->stream));
+    HIPCHK(c, c->k_tick.reserve((size_t)n));
+    HIPCHK(c, c->k_oflags.reserve((size_t)n));
+    HIPCHK(c, owgs_launch_throttle(c->k_act.p, c->k_r0.p, n, bits, c->q_temp.p, tb, c->q_key.p, c->q_idx0.p,
+                                   c->q_idx1.p, c->d_ns_active.p, c->k_tick.p, c->k_oflags.p, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_count, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_ok, c->k_oflags.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return OWGS_OK;
 }
 

@@ -563,8 +563,26 @@ struct OwgsActTable {
     unsigned long long* tw;      // 0 empty, 1 ready, 2 deleted, 1 << 63 | batch index = claimed by an insert batch
     ulonglong2* tk;              // activation id
     int2* tv;                    // {action handle, caller ticket}
+    int32_t* tn;                 // namespace handle of the entry's first tracker (ActivationEntry.namespaceId, CLB:157);
+                                 // OWGS_NONE_V when it was tracked without one
     int32_t* owner;              // lowest batch index of a slot's inserts / removals (INT_MAX between calls)
     long long cap;
+};
+
+// The controller's in-flight books (CLB:62-65) as the track / completion kernels see them.  active = the dense
+// per-namespace counters (activationsPerNamespace: int32, wrapping = LongAdder.intValue, CLB:84), null while no
+// namespace is registered.  The memory totals leave each call as two words of megabytes summed over the items the call
+// counted (cnt[OWGS_CNT_MANAGED_MB], cnt[OWGS_CNT_BLACKBOX_MB], beside the entries inserted / removed); the host adds
+// them to (track) or subtracts them from (completion) its int64 totals after the synchronisation the call already has.
+#define OWGS_CNT_INSERTED 0
+#define OWGS_CNT_REMOVED 1
+#define OWGS_CNT_MANAGED_MB 2
+#define OWGS_CNT_BLACKBOX_MB 3
+#define OWGS_CNT_WORDS 4
+struct OwgsInflight {
+    int32_t* active;
+    const int32_t* act_mem;      // action.limits.memory.megabytes by action handle
+    const uint8_t* act_bb;       // action.exec.pull by action handle
 };
 
 struct OwgsAckCompleteArgs {
@@ -580,7 +598,8 @@ struct OwgsAckCompleteArgs {
     int32_t *r_inv, *r_mem, *r_maxc, *r_slot;   // release records (owgs_release_seq_kernel input)
     uint8_t* out_kind;
     int32_t* out_ticket;
-    unsigned long long* counters;               // [0] entries inserted, [1] entries removed
+    unsigned long long* counters;               // [OWGS_CNT_WORDS]: entries removed, MB of the removed entries
+    OwgsInflight fl;
 };
 
 // ActivationMessage serialisation + topic fan-out (owgs_msgs.hip); every pointer is device memory
