@@ -706,6 +706,8 @@ static int reset_ctab(owgs_ctx* c) {
     }
     c->ovf_used_ub = 0;
     ovf_probes_clear(c);
+    // the chunked engine's rebuild mark names a table that is gone: as if never rebuilt
+    HIPCHK(c, hipMemsetAsync(c->d_clast.p, 0, sizeof(int32_t), c->stream));
     return OWGS_OK;
 }
 
@@ -1081,6 +1083,14 @@ static void res_reap(owgs_ctx* c) {
         ++c->res_n_life;
     c->res_ctl[OWGS_RES_STATE] = 0;
 }
+// the exited engine wrote its primary table back, possibly compacted by its cleanup between calls: the chunked engine's
+// rebuild mark (d_clast) describes the table before that and would delay the next rebuild.  (The engine's stream has
+// drained and no chunked launch runs beside a live resident engine.)
+static int res_clear_mark(owgs_ctx* c) {
+    HIPCHK(c, hipMemsetAsync(c->d_clast.p, 0, sizeof(int32_t), c->res_stream));
+    HIPCHK(c, hipStreamSynchronize(c->res_stream));
+    return OWGS_OK;
+}
 static int res_quiesce(owgs_ctx* c) {
     if (!c->res_alive) return OWGS_OK;
     __atomic_store_n(&c->res_ctl[OWGS_RES_BELL], -1, __ATOMIC_RELEASE);
@@ -1088,7 +1098,7 @@ static int res_quiesce(owgs_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->res_stream));
     res_reap(c);
     if (c->w_cap > 0 && c->w_live <= 0) w_drop(c);  // the engine's calls took the last pairs out of W
-    return OWGS_OK;
+    return res_clear_mark(c);
 }
 
 #define OWGS_ENTER(c)                             \
@@ -1437,6 +1447,7 @@ static int res_process(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, cons
         HIPCHK(c, hipStreamSynchronize(c->res_stream));
         res_reap(c);
         c->res_alive = false;
+        if (const int rm = res_clear_mark(c)) return rm;
         if (attempt >= 3) return c->fail(OWGS_EDEVICE, "resident engine exits before serving a call");
         const int rc = res_launch(c);
         if (rc) return rc;

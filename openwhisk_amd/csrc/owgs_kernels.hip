@@ -429,63 +429,84 @@ __device__ __forceinline__ void lds_dma4_l2(const void* gsrc, uint32_t lds_dst) 
 
 // ------------------------------------------------------------------------------------------------ LDS layout
 #define OWGS_NSTG 3  // chunk staging buffers
+// Every region whose size depends only on the geometry sits at a compile-time offset from the start of the dynamic LDS,
+// so the body addresses it with constants (ds_* offset immediates reach 65,535 bytes: the scalars, ccw, stgC, the
+// per-pass scratch union, stgX, stgL and the base of ct lie below that; stgA lies above).  The regions sized by the
+// state -- permits P, the pool words or the usable bitmap, the bitmap's prefix counts -- follow the fixed part, P at a
+// constant offset too.  Every region starts on a 16-byte boundary (uint4 / int4 accesses, LDS-DMA destinations).
+#define OWGS_AL(x) (((uint32_t)(x) + 15u) & ~15u)
+constexpr uint32_t LY_SC = 0u;                                       // LDS scalars (SC_N words, padded to 16 bytes)
+constexpr uint32_t LY_CCW = LY_SC + OWGS_AL(4u * SC_N);              // per chunk: walk cursor + committed lanes of each action, at its first lane
+constexpr uint32_t LY_STGC = LY_CCW + 4u * OWGS_WL;                  // HBM walk cursors of chunks g and g+1, gathered by the I/O wave
+// phase union: acquire phase {fst, spt, hot directory, hot rank tables, hot scratch, ...} / release phase {rc}
+constexpr uint32_t LY_UNI = LY_STGC + 2u * OWGS_WL * 4u;
+constexpr uint32_t LY_FST = LY_UNI;
+constexpr uint32_t LY_SPT = LY_FST + 4u * OWGS_NBK;
+constexpr uint32_t LY_HDIR = LY_SPT + 4u * OWGS_WL;                  // NHOT x {action, meta.x, meta.y, slot}, NHOT x max occ, NHOT x flag
+constexpr uint32_t LY_HTAB = LY_HDIR + 24u * NHOT;                   // NHOT x HOT_RANKS x {id | kind << 15 | ks << 18, step}
+constexpr uint32_t LY_HSCR = LY_HTAB + 8u * NHOT * HOT_RANKS;        // (OWGS_EW + 1) x 64 rank marks (the I/O wave walks hot slots too)
+constexpr uint32_t LY_BHEAD = LY_HSCR + 4u * 64 * (OWGS_EW + 1);     // per pass: lanes of each bucket (list head, lane + 1)
+constexpr uint32_t LY_NEXTL = LY_BHEAD + 4u * OWGS_NBK;              // next lane of the bucket list (lane + 1, 0 = end)
+constexpr uint32_t LY_SPC = LY_NEXTL + 4u * OWGS_WL;                 // memory each lane tentatively takes at its target
+constexpr uint32_t LY_CDIRTY = LY_SPC + 4u * OWGS_WL;                // [2][OWGS_WL] bytes, pass parity x first lane of an action: re-speculated
+constexpr uint32_t LY_SKEY = LY_CDIRTY + 2u * OWGS_WL;               // per lane {slot key, action} (shared-key check)
+constexpr uint32_t LY_LQ = LY_SKEY + 8u * OWGS_WL;                   // long-walk queue: {record | rank, step, position, cum} / result
+constexpr uint32_t LY_FXA = LY_LQ + 16u * OWGS_WL;                   // per lane: validation summary / in-pass re-decision (OWGS_EXT)
+constexpr uint32_t LY_UNI_BYTES = LY_FXA + 16u * OWGS_WL - LY_UNI;
+constexpr uint32_t LY_RC = LY_UNI;                                   // release phase: one counter per concurrency-table entry
+constexpr uint32_t LY_STGX = LY_UNI + LY_UNI_BYTES;                  // release slots of 3 chunks (g, g+1 staged, g+2 streaming in)
+constexpr uint32_t LY_STGL = LY_STGX + OWGS_NSTG * OWGS_WL * 4u;     // their lane indices
+constexpr uint32_t LY_CT = LY_STGL + OWGS_NSTG * OWGS_WL * 4u;       // concurrency table, interleaved {key, value}
+constexpr uint32_t LY_STGA = LY_CT + 8u * OWGS_CTC;                  // their records (16 bytes each)
+constexpr uint32_t LY_P = LY_STGA + OWGS_NSTG * OWGS_WL * 16u;       // end of the fixed part: permits, then pool, then pc
+static_assert(LY_UNI_BYTES >= 4u * OWGS_CTC, "the release counters overlay the per-pass scratch");
+static_assert((2u * OWGS_WL) % 16u == 0 && (4u * OWGS_NBK) % 16u == 0 && (24u * NHOT) % 16u == 0, "16-byte regions");
+static_assert(LY_CCW % 16u == 0 && LY_STGC % 16u == 0 && LY_UNI % 16u == 0 && LY_HDIR % 16u == 0 && LY_LQ % 16u == 0 &&
+                  LY_FXA % 16u == 0 && LY_STGX % 16u == 0 && LY_STGL % 16u == 0 && LY_CT % 16u == 0 && LY_STGA % 16u == 0 &&
+                  LY_P % 16u == 0,
+              "uint4 regions and LDS-DMA destinations start on 16 bytes");
+static_assert(LY_CT <= 65535u, "the regions read in every phase stay within reach of a ds offset immediate");
+
+// the state-sized tail
 struct OwgsLayout {
-    uint32_t P, pool, pc, ccw, ct, stgA, stgX, stgL, stgC, fst, spt, hdir, htab, hscr, bhead, nextl, spc, cdirty, skey, lq, fxa, rc, sc,
-        uni, uni_bytes, total;
+    uint32_t pool, pc, total;
 };
 
-__host__ __device__ inline OwgsLayout owgs_layout(int n_slots, int pool_mode, int n_ids, int nm, int nb, int n_actions) {
+__host__ __device__ inline OwgsLayout owgs_layout(int n_slots, int pool_mode, int n_ids, int nm, int nb) {
     OwgsLayout L;
-    uint32_t o = 0;
-#define OWGS_AL(x) (((uint32_t)(x) + 15u) & ~15u)
     const uint32_t words = (uint32_t)(n_ids + 31) / 32;
-    L.P = o;
-    o += OWGS_AL(4u * (uint32_t)n_slots);
-    L.pool = o;
-    o += pool_mode ? OWGS_AL(2u * (uint32_t)(nm + nb)) : OWGS_AL(4u * words);
-    L.pc = o;  // identity pools: usable ids before each bitmap word (rank/select for the fallback)
-    o += pool_mode ? 0u : OWGS_AL(4u * (words + 1));
-    (void)n_actions;  // per-action state lives in HBM (walk cursors: A.gcur)
-    L.ccw = o;        // per chunk: walk cursor + committed lanes of each action, at its first lane
-    o += 4u * OWGS_WL;
-    L.ct = o;
-    o += 8u * OWGS_CTC;
-    L.stgA = o;  // records, lane indices and release slots of 3 chunks (g, g+1 staged, g+2 streaming in)
-    o += OWGS_NSTG * OWGS_WL * 16u;
-    L.stgX = o;
-    o += OWGS_NSTG * OWGS_WL * 4u;
-    L.stgL = o;
-    o += OWGS_NSTG * OWGS_WL * 4u;
-    L.stgC = o;  // HBM walk cursors of chunks g and g+1, gathered by the I/O wave
-    o += 2u * OWGS_WL * 4u;
-    L.sc = o;
-    o += 4u * SC_N;
-    // phase union: acquire phase {fst, spt, hot directory, hot rank tables, hot scratch} / release phase {rc}
-    L.uni = o;
-    L.fst = o;
-    L.spt = o + 4u * OWGS_NBK;
-    L.hdir = L.spt + 4u * OWGS_WL;                  // NHOT x {action, meta.x, meta.y, slot}, NHOT x max occ, NHOT x flag
-    L.htab = L.hdir + 24u * NHOT;                   // NHOT x HOT_RANKS x {id | kind << 15 | ks << 18, step}
-    L.hscr = L.htab + 8u * NHOT * HOT_RANKS;        // (OWGS_EW + 1) x 64 rank marks (the I/O wave walks hot slots too)
-    L.bhead = L.hscr + 4u * 64 * (OWGS_EW + 1);     // per pass: lanes of each bucket (list head, lane + 1)
-    L.nextl = L.bhead + 4u * OWGS_NBK;              // next lane of the bucket list (lane + 1, 0 = end)
-    L.spc = L.nextl + 4u * OWGS_WL;                 // memory each lane tentatively takes at its target
-    L.cdirty = L.spc + 4u * OWGS_WL;                // [2][OWGS_WL] pass parity x first lane of an action: re-speculated
-    L.skey = L.cdirty + 8u * OWGS_WL;               // per lane {slot key, action} (shared-key check)
-    L.lq = L.skey + 8u * OWGS_WL;                   // long-walk queue: {record | rank, step, position, cum} / result
-    L.fxa = L.lq + 16u * OWGS_WL;                  // per lane: validation summary / in-pass re-decision (OWGS_EXT)
-    L.rc = o;
-    const uint32_t ua = (L.fxa - o) + 16u * OWGS_WL, ur = 4u * OWGS_CTC;
-    L.uni_bytes = ua > ur ? ua : ur;
-    o += L.uni_bytes;
-    L.total = o;
-#undef OWGS_AL
+    L.pool = LY_P + OWGS_AL(4u * (uint32_t)n_slots);
+    L.pc = L.pool + (pool_mode ? OWGS_AL(2u * (uint32_t)(nm + nb)) : OWGS_AL(4u * words));
+    // identity pools: usable ids before each bitmap word (rank/select for the fallback)
+    L.total = L.pc + (pool_mode ? 0u : OWGS_AL(4u * (words + 1)));
     return L;
 }
 
 extern "C" size_t OWGS_GEOM(owgs_engine_lds_bytes)(int n_slots, int pool_mode, int n_ids, int nm, int nb, int n_actions) {
-    return owgs_layout(n_slots, pool_mode, n_ids, nm, nb, n_actions).total;
+    (void)n_actions;  // per-action state lives in HBM (walk cursors: A.gcur)
+    return owgs_layout(n_slots, pool_mode, n_ids, nm, nb).total;
 }
+
+// The image's regions in address order, for checks of the layout: out[2 * i] = offset, out[2 * i + 1] = bytes of region
+// i (sc, ccw, stgC, fst, spt, hdir, htab, hscr, bhead, nextl, spc, cdirty, skey, lq, fxa, stgX, stgL, ct, stgA, P, pool,
+// pc), then {total, 0}.  Writes at most cap pairs; returns the number of pairs the image has.
+extern "C" int OWGS_GEOM(owgs_engine_lds_regions)(int n_slots, int pool_mode, int n_ids, int nm, int nb, uint32_t* out, int cap) {
+    const OwgsLayout Y = owgs_layout(n_slots, pool_mode, n_ids, nm, nb);
+    const uint32_t off[] = {LY_SC,  LY_CCW,    LY_STGC, LY_FST, LY_SPT, LY_HDIR, LY_HTAB, LY_HSCR, LY_BHEAD, LY_NEXTL, LY_SPC, LY_CDIRTY,
+                            LY_SKEY, LY_LQ,    LY_FXA,  LY_STGX, LY_STGL, LY_CT, LY_STGA, LY_P,    Y.pool,   Y.pc,     Y.total};
+    const uint32_t words = (uint32_t)(n_ids + 31) / 32;
+    const uint32_t used_tail[] = {4u * (uint32_t)n_slots, pool_mode ? 2u * (uint32_t)(nm + nb) : 4u * words,
+                                  pool_mode ? 0u : 4u * (words + 1)};
+    const int n = (int)(sizeof(off) / sizeof(off[0]));
+    for (int i = 0; i < n && i < cap; ++i) {
+        out[2 * i] = off[i];
+        // fixed regions fill the space up to the next one, except sc (its last 8 bytes are padding); the tail regions
+        // report the bytes they use
+        out[2 * i + 1] = i == n - 1 ? 0u : i == 0 ? 4u * SC_N : i >= n - 4 ? used_tail[i - (n - 4)] : off[i + 1] - off[i];
+    }
+    return n;
+}
+#undef OWGS_AL
 
 // ------------------------------------------------------------------------------------------------ hashing
 __device__ __forceinline__ uint32_t pow31(uint32_t k) {
@@ -1110,7 +1131,11 @@ __device__ __forceinline__ void lds_sync() {
 #define TRACE_MARK(id)
 #endif
 
-template <int FEAT>
+// IO: the body of the I/O wave (wave OWGS_EW) or of the engine waves.  Both come from this one source, so every barrier
+// (lds_sync, LDS_SYNC_T, __syncthreads) is reached the same number of times by both; the hardware barrier counts
+// arriving waves, not program locations.  No barrier may stand under a condition on the role, and the early returns
+// (OWGS_ERR_GEOM, OWGS_ERR_RELRISK) are uniform over the workgroup.
+template <int FEAT, bool IO>
 __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
     // specialisation (OWGS_F_*): without F_CONC every lane is maxConcurrent == 1 (a record saying otherwise is a broken
     // stream) and the map code is gone; without F_GEN pools are identity pools and sequence numbers implicit
@@ -1139,40 +1164,40 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
 #endif
     extern __shared__ uint4 lds_raw[];
     char* L = (char*)lds_raw;
-    const OwgsLayout Y = owgs_layout(A.n_slots, pool_mode, A.n_ids, A.nm, A.nb, A.n_actions);
-    int32_t* P = (int32_t*)(L + Y.P);
+    const OwgsLayout Y = owgs_layout(A.n_slots, pool_mode, A.n_ids, A.nm, A.nb);  // (the state-sized tail only)
+    int32_t* P = (int32_t*)(L + LY_P);
     uint32_t* ub = (uint32_t*)(L + Y.pool);
     int16_t* pw = (int16_t*)(L + Y.pool);
     uint32_t* pc = (uint32_t*)(L + Y.pc);
-    uint32_t* ccw = (uint32_t*)(L + Y.ccw);
-    const uint32_t* stgC = (const uint32_t*)(L + Y.stgC);
-    uint2* ct = (uint2*)(L + Y.ct);  // interleaved {key, value}
-    uint4* stgA = (uint4*)(L + Y.stgA);
-    int32_t* stgX = (int32_t*)(L + Y.stgX);
-    uint32_t* fst = (uint32_t*)(L + Y.fst);
-    int32_t* spt = (int32_t*)(L + Y.spt);
-    uint32_t* bhead = (uint32_t*)(L + Y.bhead);
-    int32_t* nextl = (int32_t*)(L + Y.nextl);
-    int32_t* spc = (int32_t*)(L + Y.spc);
-    int32_t* cdirty = (int32_t*)(L + Y.cdirty);
-    uint2* skey = (uint2*)(L + Y.skey);
-    uint4* lq = (uint4*)(L + Y.lq);
-    uint4* fxa = (uint4*)(L + Y.fxa);
-    uint4* hdir = (uint4*)(L + Y.hdir);
-    int32_t* hocc = (int32_t*)(L + Y.hdir + 16u * NHOT);
-    int32_t* hflag = (int32_t*)(L + Y.hdir + 20u * NHOT);
-    uint2* htab = (uint2*)(L + Y.htab);
-    int32_t* hscr = (int32_t*)(L + Y.hscr);
-    const uint32_t* stgL = (const uint32_t*)(L + Y.stgL);
-    uint32_t* rc = (uint32_t*)(L + Y.rc);
-    int32_t* sc = (int32_t*)(L + Y.sc);
+    uint32_t* ccw = (uint32_t*)(L + LY_CCW);
+    const uint32_t* stgC = (const uint32_t*)(L + LY_STGC);
+    uint2* ct = (uint2*)(L + LY_CT);  // interleaved {key, value}
+    uint4* stgA = (uint4*)(L + LY_STGA);
+    int32_t* stgX = (int32_t*)(L + LY_STGX);
+    uint32_t* fst = (uint32_t*)(L + LY_FST);
+    int32_t* spt = (int32_t*)(L + LY_SPT);
+    uint32_t* bhead = (uint32_t*)(L + LY_BHEAD);
+    int32_t* nextl = (int32_t*)(L + LY_NEXTL);
+    int32_t* spc = (int32_t*)(L + LY_SPC);
+    uint8_t* cdirty = (uint8_t*)(L + LY_CDIRTY);
+    uint2* skey = (uint2*)(L + LY_SKEY);
+    uint4* lq = (uint4*)(L + LY_LQ);
+    uint4* fxa = (uint4*)(L + LY_FXA);
+    uint4* hdir = (uint4*)(L + LY_HDIR);
+    int32_t* hocc = (int32_t*)(L + LY_HDIR + 16u * NHOT);
+    int32_t* hflag = (int32_t*)(L + LY_HDIR + 20u * NHOT);
+    uint2* htab = (uint2*)(L + LY_HTAB);
+    int32_t* hscr = (int32_t*)(L + LY_HSCR);
+    const uint32_t* stgL = (const uint32_t*)(L + LY_STGL);
+    uint32_t* rc = (uint32_t*)(L + LY_RC);
+    int32_t* sc = (int32_t*)(L + LY_SC);
 #ifdef OWGS_PROFILE
     int* spw = sc + 16;
     int* pfw = sc + 16 + 4 * OWGS_EW;  // per-wave speculation timings (SC_N leaves room in every build)
 #endif
 
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const bool io = wave >= OWGS_EW;
+    const int tid = threadIdx.x, wave = IO ? OWGS_EW : tid >> 6, lane = tid & 63;
+    constexpr bool io = IO;
     const int n_slots = A.n_slots, nm = A.nm, nb = A.nb;
     const int words = (A.n_ids + 31) >> 5;
 
@@ -1262,7 +1287,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
         if (used) atomicAdd(&sc[SC_USED], used);
         if (tid == 0 && A.ovf.cap > 0) sc[SC_OVF] = __hip_atomic_load(A.ovf.cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    for (int i = tid; i < (int)(Y.uni_bytes / 4); i += OWGS_NT) ((uint32_t*)(L + Y.uni))[i] = 0u;
+    for (int i = tid; i < (int)(LY_UNI_BYTES / 4); i += OWGS_NT) ((uint32_t*)(L + LY_UNI))[i] = 0u;
     lds_sync();
     // the table's fill after its last rebuild (an earlier launch's; fewer entries now: rebuilt elsewhere since)
     if (tid == 0 && A.ct_clast) sc[SC_CLAST] = min(*A.ct_clast, sc[SC_USED]);
@@ -3216,6 +3241,15 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
     }
 }
 
+// the role of this wave, as a scalar: the kernels branch on it once (s_cbranch) into the body of that role
+__device__ __forceinline__ bool owgs_io_wave() {
+#ifdef OWGS_ROLE_ONLY  // (tools/engine_isa.py) one role's body alone, to read its static counts; never in the library
+    return OWGS_ROLE_ONLY != 0;
+#else
+    return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) >= OWGS_EW;
+#endif
+}
+
 // one shard: the argument block behind a (uniform) workgroup index, like the multi-shard kernel -- read from the
 // kernarg segment where each phase needs it instead of held in registers across the whole body (a by-value block
 // is hoisted: 256 VGPRs with scratch spills against 233 without)
@@ -3223,7 +3257,10 @@ struct OwgsEngineOne {
     OwgsEngineArgs a[1];
 };
 template <int FEAT>
-__global__ __launch_bounds__(OWGS_NT, 1) void owgs_engine_kernel(OwgsEngineOne M) { owgs_engine_body<FEAT>(M.a[blockIdx.x]); }
+__global__ __launch_bounds__(OWGS_NT, 1) void owgs_engine_kernel(OwgsEngineOne M) {
+    if (owgs_io_wave()) owgs_engine_body<FEAT, true>(M.a[blockIdx.x]);
+    else owgs_engine_body<FEAT, false>(M.a[blockIdx.x]);
+}
 
 // several controller shards in one launch: workgroup k replays shard k (its own LDS image, state and stream); the
 // arguments stay in the kernarg segment, so every field is still a scalar load
@@ -3232,12 +3269,14 @@ struct OwgsEngineMulti {
 };
 template <int FEAT>
 __global__ __launch_bounds__(OWGS_NT, 1) void owgs_engine_multi_kernel(OwgsEngineMulti M) {
-    owgs_engine_body<FEAT>(M.a[blockIdx.x]);
+    if (owgs_io_wave()) owgs_engine_body<FEAT, true>(M.a[blockIdx.x]);
+    else owgs_engine_body<FEAT, false>(M.a[blockIdx.x]);
 }
 // more shards than the kernarg segment holds: the argument blocks in HBM (uniform per workgroup, read-only)
 template <int FEAT>
 __global__ __launch_bounds__(OWGS_NT, 1) void owgs_engine_multi_dev_kernel(const OwgsEngineArgs* __restrict__ As) {
-    owgs_engine_body<FEAT>(As[blockIdx.x]);
+    if (owgs_io_wave()) owgs_engine_body<FEAT, true>(As[blockIdx.x]);
+    else owgs_engine_body<FEAT, false>(As[blockIdx.x]);
 }
 
 // ------------------------------------------------------------------------------------------------ explicit releases
