@@ -326,6 +326,60 @@ int owgs_activation_totals(owgs_ctx* ctx, int64_t out[3]);
 int owgs_throttle_batch(owgs_ctx* ctx, int32_t n, const int32_t* ns, const int32_t* limit, int32_t* out_count,
                         uint8_t* out_ok);
 
+/* ---- completion-ack timeouts (CLB:103-105, 148-152) ----
+ * setupActivation arms one timer per ActivationEntry inside getOrElseUpdate (CLB:148-152); a regular ack cancels it
+ * (CLB:289); a fired timer runs processCompletion(aid, tid, forced = true, isSystemError = false, invoker =
+ * entry.invoker), which removes the entry, takes it out of the books, releases the invoker and sends
+ * InvocationFinishedMessage(invoker, Timeout) (CLB:266-267, 278-317).  Here the deadline and the entry's invoker are
+ * stored with the entry, and one call fires everything that is due.  An entry a regular ack removed has no deadline
+ * left, so a sweep never produces OWGS_ACK_FORCED_NOENTRY; a regular ack that arrives after the sweep gets
+ * OWGS_ACK_NOENTRY (CLB:329-337).  Entries tracked through owgs_track_activations / owgs_track_activations_ns never
+ * expire; owgs_complete_activations with the forced bit keeps working for callers that keep their own timers.
+ *
+ * Order.  The reference pins no order among akka timers that are due together.  This project defines one: ascending
+ * (deadline, arm order), where arm order is the order in which the entries were created -- track call order, then
+ * array index within a call.  Within one sweep it shows in the output arrays, in which release sees a
+ * ForcibleSemaphore overflow, and in the rank-dependent concurrent releases. */
+
+/* calculateCompletionAckTimeout (CLB:103-105): TimeLimit.STD_DURATION, lbConfig.timeoutFactor, lbConfig.timeoutAddon.
+ * Defaults 60000, 2, 60000 (TimeLimit std 1 minute; reference.conf timeout-factor 2, timeout-addon 1m).  std_ms and
+ * addon_ms in [0, 2^40), factor in [1, 2^16), else OWGS_EINVAL.  Applies to entries armed afterwards. */
+int owgs_set_ack_timeout(owgs_ctx* ctx, int64_t std_ms, int32_t factor, int64_t addon_ms);
+
+/* owgs_track_activations_ns plus the entry's invoker (ActivationEntry.invoker, CLB:158) and its action time limit
+ * (ActivationEntry.timeLimit, CLB:160).  The item that CREATES an entry arms its deadline
+ *   now_ms + max(time_limit_ms[i], std_ms) * factor + addon_ms
+ * An item whose id already has an entry arms nothing (the by-name block of getOrElseUpdate does not run, CLB:148-152);
+ * it is still counted by the books, as today.  ns may be NULL (every item OWGS_NONE).  now_ms in [0, 2^60),
+ * time_limit_ms[i] in [0, 2^40), invoker[i] >= 0, else OWGS_EINVAL; unknown handles and malformed ids as in
+ * owgs_track_activations_ns; a rejected batch changes nothing. */
+int owgs_track_activations_timed(owgs_ctx* ctx, int32_t n, const char* aid32, const int32_t* action,
+                                 const int32_t* ns, const int32_t* ticket, const int32_t* invoker,
+                                 const int64_t* time_limit_ms, int64_t now_ms, int32_t* out_ticket,
+                                 uint8_t* out_existed);
+
+/* Every timer due at or before now_ms fires: processCompletion(aid, tid, forced = true, isSystemError = false,
+ * invoker = entry.invoker) (CLB:150-152, 260-317) for each live entry with deadline <= now_ms, in ascending
+ * (deadline, arm order), at most cap of them.  *out_n = entries expired by this call, *out_remaining = due entries left
+ * armed because of cap (cap = 0: the due count, nothing expires; the output arrays may then be NULL).  out_aid = 2
+ * words (hi, lo) per entry; out_flags = the release flags of releaseInvoker << 1 as in owgs_process_acks.  An entry
+ * invoker beyond invokerSlots is a no-op release (lift, SCPB:329).  feed_health != 0: the expired entries'
+ * InvocationFinishedMessage(invoker, Timeout) (CLB:317) go to the device health FSM as OWGS_EV_TIMEOUT events at time
+ * now_ms in the same order, with apply = 0 (a sweep that expires nothing feeds nothing and leaves the FSM's clock
+ * alone); now_ms before the FSM's last now_ms is then OWGS_EINVAL with nothing expired.  now_ms in [0, 2^60),
+ * cap >= 0. */
+int owgs_expire_activations(owgs_ctx* ctx, int64_t now_ms, int32_t cap, int32_t feed_health, int32_t* out_n,
+                            int64_t* out_remaining, uint64_t* out_aid, int32_t* out_ticket, int32_t* out_invoker,
+                            int64_t* out_deadline, uint8_t* out_flags);
+
+/* A lower bound of the earliest armed deadline (INT64_MAX: none): what the shim sleeps until.  It may be earlier than
+ * the true minimum after regular acks removed entries; a sweep makes it exact for every tile it scanned. */
+int owgs_next_deadline(owgs_ctx* ctx, int64_t* t_ms);
+
+/* out[0] sweeps, [1] tiles scanned over all sweeps, [2] tiles scanned by the last sweep, [3] entries expired over all
+ * sweeps, [4] tiles of the current table (1,024 slots each; 0 before the table exists). */
+int owgs_expiry_stats(owgs_ctx* ctx, int64_t out[5]);
+
 /* ---- invoker health supervision ----
  * Replaces: InvokerPool (InvokerSupervision.scala:95-210: registerInvoker on the first ping, padToIndexed with Offline
  * entries, InvocationFinishedMessage forwarding) and one InvokerActor FSM per invoker (InvokerSupervision.scala:

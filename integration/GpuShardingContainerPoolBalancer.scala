@@ -57,6 +57,18 @@ object OwgsNative {
                            seqBase: Long): Int
   /** owgs_release_actions: handles of cold fqn@version keys (none of their activations in flight) */
   @native def releaseActions(ctx: Long, handles: Array[Int], n: Int): Int
+  /** owgs_track_activations_timed: setupActivation's getOrElseUpdate with the entry's invoker and time limit, so that
+   *  the completion-ack timeout (CLB:103-105, 148-152) is armed on the device; ns may be null. */
+  @native def trackActivationsTimed(ctx: Long, aid32: Array[Byte], actions: Array[Int], ns: Array[Int],
+                                    tickets: Array[Int], invokers: Array[Int], timeLimitMs: Array[Long], n: Int,
+                                    nowMs: Long, outTicket: Array[Int], outExisted: Array[Byte]): Int
+  /** owgs_expire_activations: every timer due at nowMs fires, at most cap of them, in (deadline, arm order);
+   *  outCounts(0) = expired, outCounts(1) = due entries left; outAid holds (hi, lo) per expired entry. */
+  @native def expireActivations(ctx: Long, nowMs: Long, cap: Int, feedHealth: Boolean, outCounts: Array[Long],
+                                outAid: Array[Long], outTicket: Array[Int], outInvoker: Array[Int],
+                                outDeadline: Array[Long], outFlags: Array[Byte]): Int
+  /** owgs_next_deadline: a lower bound of the earliest armed deadline (Long.MaxValue: none; negative: an error) */
+  @native def nextDeadline(ctx: Long): Long
   @native def lastError(ctx: Long): String
 }
 

@@ -248,6 +248,74 @@ JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00
     return rc;
 }
 
+/* ---- completion-ack timeouts on the device (CLB:103-105, 148-152): owgs_track_activations_timed and the sweep ---- */
+/* ns may be null (every item without a namespace) */
+JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_trackActivationsTimed(
+    JNIEnv* env, jobject self, jlong h, jbyteArray aid32, jintArray actions, jintArray ns, jintArray tickets,
+    jintArray invokers, jlongArray timeLimitMs, jint n, jlong nowMs, jintArray outTicket, jbyteArray outExisted) {
+    if (!aid32 || !actions || !tickets || !invokers || !timeLimitMs || !outTicket || !outExisted ||
+        !n_fits(env, n, actions, tickets, invokers, timeLimitMs) || !n_fits(env, n, ns, outTicket, outExisted, NULL) ||
+        !n_fits(env, 32LL * n, aid32, NULL, NULL, NULL))
+        return OWGS_EINVAL;
+    char* pa = jcopy_in(env, aid32, 32LL * n, 1, 'B');
+    int32_t* pc = jcopy_in(env, actions, n, 4, 'I');
+    int32_t* pn = ns ? jcopy_in(env, ns, n, 4, 'I') : NULL;
+    int32_t* pt = jcopy_in(env, tickets, n, 4, 'I');
+    int32_t* pi = jcopy_in(env, invokers, n, 4, 'I');
+    int64_t* pl = jcopy_in(env, timeLimitMs, n, 8, 'J');
+    int32_t* po = calloc((size_t)(n > 0 ? n : 1), 4);
+    uint8_t* pe = calloc((size_t)(n > 0 ? n : 1), 1);
+    int rc = OWGS_ENOMEM;
+    if (pa && pc && (pn || !ns) && pt && pi && pl && po && pe)
+        rc = owgs_track_activations_timed(CTX(h), n, pa, pc, pn, pt, pi, pl, nowMs, po, pe);
+    if (rc == OWGS_OK) {
+        jcopy_out(env, outTicket, n, po, 'I');
+        jcopy_out(env, outExisted, n, pe, 'B');
+    }
+    FREE_ALL(pa, pc, pn, pt, pi, pl, po, pe);
+    return rc;
+}
+
+/* one sweep: outCounts[0] = entries expired (<= cap), outCounts[1] = due entries left armed because of cap; outAid
+ * holds two longs (hi, lo) per expired entry */
+JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_expireActivations(
+    JNIEnv* env, jobject self, jlong h, jlong nowMs, jint cap, jboolean feedHealth, jlongArray outCounts,
+    jlongArray outAid, jintArray outTicket, jintArray outInvoker, jlongArray outDeadline, jbyteArray outFlags) {
+    if (!outCounts || !outAid || !outTicket || !outInvoker || !outDeadline || !outFlags ||
+        !n_fits(env, cap, outTicket, outInvoker, outDeadline, outFlags) ||
+        !n_fits(env, 2LL * cap, outAid, NULL, NULL, NULL) || !n_fits(env, 2, outCounts, NULL, NULL, NULL))
+        return OWGS_EINVAL;
+    uint64_t* pa = calloc((size_t)(cap > 0 ? cap : 1), 16);
+    int32_t* pt = calloc((size_t)(cap > 0 ? cap : 1), 4);
+    int32_t* pi = calloc((size_t)(cap > 0 ? cap : 1), 4);
+    int64_t* pd = calloc((size_t)(cap > 0 ? cap : 1), 8);
+    uint8_t* pf = calloc((size_t)(cap > 0 ? cap : 1), 1);
+    int32_t n = 0;
+    int64_t counts[2] = {0, 0};
+    int rc = OWGS_ENOMEM;
+    if (pa && pt && pi && pd && pf)
+        rc = owgs_expire_activations(CTX(h), nowMs, cap, feedHealth ? 1 : 0, &n, &counts[1], pa, pt, pi, pd, pf);
+    if (rc == OWGS_OK) {
+        counts[0] = n;
+        jcopy_out(env, outCounts, 2, counts, 'J');
+        jcopy_out(env, outAid, 2LL * n, pa, 'J');
+        jcopy_out(env, outTicket, n, pt, 'I');
+        jcopy_out(env, outInvoker, n, pi, 'I');
+        jcopy_out(env, outDeadline, n, pd, 'J');
+        jcopy_out(env, outFlags, n, pf, 'B');
+    }
+    FREE_ALL(pa, pt, pi, pd, pf);
+    return rc;
+}
+
+/* owgs_next_deadline: what the batcher sleeps until (Long.MaxValue: nothing armed); a negative value is an error code */
+JNIEXPORT jlong JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_nextDeadline(
+    JNIEnv* env, jobject self, jlong h) {
+    int64_t t = 0;
+    const int rc = owgs_next_deadline(CTX(h), &t);
+    return rc == OWGS_OK ? (jlong)t : (jlong)rc;
+}
+
 /* ---- invoker health supervision (InvokerPool + InvokerActor) ---- */
 JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_healthEvents(
     JNIEnv* env, jobject self, jlong h, jintArray invokers, jbyteArray kinds, jlongArray tMs, jlongArray userMemory,

@@ -22,6 +22,8 @@ FLAG_OVERLOAD = 1
 REL_NOSUCHELEMENT, REL_OVERFLOW, REL_NOENTRY = 1, 2, 4
 ACK_FAIL, ACK_JVM, ACK_UNSUPPORTED, ACK_RELEASED, ACK_HEALTH, ACK_NOENTRY, ACK_FORCED_NOENTRY = range(7)
 HEALTHY, UNHEALTHY, UNRESPONSIVE, OFFLINE = 0, 1, 2, 3
+EV_PING, EV_SUCCESS, EV_SYSTEM_ERROR, EV_TIMEOUT, EV_STATE_TIMEOUT = range(5)
+NO_DEADLINE = 2**63 - 1  # owgs_next_deadline: nothing armed
 NS_INITIAL_CAP = 1024  # OWGS_NS_INITIAL_CAP: namespaces the device counter array holds before it first grows
 
 
@@ -131,6 +133,11 @@ def lib() -> C.CDLL:
         "owgs_active_activations": (C.c_int, [P, i32, P, P]),
         "owgs_activation_totals": (C.c_int, [P, P]),
         "owgs_throttle_batch": (C.c_int, [P, i32, P, P, P, P]),
+        "owgs_set_ack_timeout": (C.c_int, [P, C.c_int64, i32, C.c_int64]),
+        "owgs_track_activations_timed": (C.c_int, [P, i32, P, P, P, P, P, P, C.c_int64, P, P]),
+        "owgs_expire_activations": (C.c_int, [P, C.c_int64, i32, i32, P, P, P, P, P, P, P]),
+        "owgs_next_deadline": (C.c_int, [P, P]),
+        "owgs_expiry_stats": (C.c_int, [P, P]),
         "owgs_replay_device": (C.c_int, [P, i32, P, P, C.c_int64, P, P, C.c_int64, u64, P, P, P, P]),
         "owgs_replay_device_multi": (C.c_int, [P, i32, P, P]),
         "owgs_replay_device_span": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P, u64, P, P, P, P]),

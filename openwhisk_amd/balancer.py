@@ -376,6 +376,69 @@ class GpuShardingContainerPoolBalancer:
         self._chk(self._L.owgs_activations_live(self._h, C.byref(v)))
         return v.value
 
+    # ------------------------------------------------------------------ completion-ack timeouts (CLB:103-105, 148-152)
+    def set_ack_timeout(self, std_ms: int = 60000, factor: int = 2, addon_ms: int = 60000):
+        """calculateCompletionAckTimeout's settings (CLB:103-105): TimeLimit.STD_DURATION, timeoutFactor, timeoutAddon."""
+        self._chk(self._L.owgs_set_ack_timeout(self._h, int(std_ms), int(factor), int(addon_ms)))
+
+    def track_activations_timed(self, aids, actions, tickets, invokers, time_limit_ms, now_ms: int, ns=None):
+        """track_activations plus the entry's invoker and its action time limit: the item that creates an entry arms
+        the deadline now_ms + max(limit, std) * factor + addon (CLB:103-105, 148-152).  (ticket, existed)."""
+        n = len(aids)
+        buf = np.frombuffer(b"".join(a.encode("ascii") for a in aids) or b"\0", dtype=np.uint8)
+        act = np.ascontiguousarray(actions, dtype=np.int32)
+        tk = np.ascontiguousarray(tickets, dtype=np.int32)
+        inv = np.ascontiguousarray(invokers, dtype=np.int32)
+        tl = np.ascontiguousarray(time_limit_ms, dtype=np.int64)
+        if not (len(act) == len(tk) == len(inv) == len(tl) == n):
+            raise ValueError("track_activations_timed: arrays of different lengths")
+        h = None
+        if ns is not None:
+            h = np.ascontiguousarray(ns, dtype=np.int32)
+            if len(h) != n:
+                raise ValueError("ns needs one handle per activation")
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        ex = np.zeros(max(n, 1), dtype=np.uint8)
+        z32, z64 = np.zeros(1, np.int32), np.zeros(1, np.int64)
+        self._chk(self._L.owgs_track_activations_timed(
+            self._h, n, _p(buf), _p(act if n else z32), _p(h if n else z32) if h is not None else None,
+            _p(tk if n else z32), _p(inv if n else z32), _p(tl if n else z64), int(now_ms), _p(out), _p(ex)))
+        return out[:n], ex[:n]
+
+    def expire_activations(self, now_ms: int, cap: int | None = None, feed_health: bool = False):
+        """Every completion-ack timer due at or before now_ms fires (forced processCompletion with the entry's invoker,
+        CLB:150-152), in ascending (deadline, arm order), at most `cap` of them (None: all):
+        (aids as 32-char strings, tickets, invokers, deadlines, flags, remaining)."""
+        if cap is None:
+            cap = self.activations_live()
+        cap = int(cap)
+        m = max(cap, 1)
+        aid = np.zeros(2 * m, dtype=np.uint64)
+        tk = np.zeros(m, dtype=np.int32)
+        inv = np.zeros(m, dtype=np.int32)
+        dl = np.zeros(m, dtype=np.int64)
+        fl = np.zeros(m, dtype=np.uint8)
+        n, rem = C.c_int32(0), C.c_int64(0)
+        self._chk(self._L.owgs_expire_activations(self._h, int(now_ms), cap, int(bool(feed_health)), C.byref(n),
+                                                  C.byref(rem), _p(aid), _p(tk), _p(inv), _p(dl), _p(fl)))
+        k = n.value
+        aids = ["%016x%016x" % (int(aid[2 * i]), int(aid[2 * i + 1])) for i in range(k)]
+        return aids, tk[:k], inv[:k], dl[:k], fl[:k], rem.value
+
+    def next_deadline(self) -> int:
+        """A lower bound of the earliest armed deadline (NO_DEADLINE = 2^63 - 1: none); exact for the tiles of the
+        table the last sweep scanned."""
+        v = C.c_int64()
+        self._chk(self._L.owgs_next_deadline(self._h, C.byref(v)))
+        return v.value
+
+    def expiry_stats(self) -> tuple[int, int, int, int, int]:
+        """(sweeps, tiles scanned over all sweeps, tiles scanned by the last sweep, entries expired, tiles of the
+        current table)."""
+        out = np.zeros(5, dtype=np.int64)
+        self._chk(self._L.owgs_expiry_stats(self._h, _p(out)))
+        return tuple(int(x) for x in out)
+
     def pairwise_coprime_numbers_until(self, x: int) -> list:
         """ShardingContainerPoolBalancer.pairwiseCoprimeNumbersUntil (SCPB:379-384), computed by owgs_coprime_kernel."""
         n = C.c_int32()

@@ -15,7 +15,9 @@
 //                            (BigDecimal.intValue), userMemory (ByteSize regex + toLong), uniqueName/displayedName
 //                            (Option[String]), isSystemError (Option[Boolean]), transid == invokerHealth.
 //   owgs_act_*_kernel        activationSlots as an open-addressing table in HBM: key = 128-bit activation id,
-//                            value = {action handle, caller ticket}.  Inserts claim an empty slot by 64-bit CAS;
+//                            value = {action handle, caller ticket} plus the entry's namespace, completion-ack
+//                            deadline, invoker and arm sequence (owgs_expire.hip sweeps the deadlines, summarised per
+//                            tile of 1,024 slots in tmin).  Inserts claim an empty slot by 64-bit CAS;
 //                            same-key inserts of one batch resolve to the lowest batch index (getOrElseUpdate in
 //                            array order); removals of one batch resolve to the lowest message index
 //                            (activationSlots.remove in array order: later duplicates see None).
@@ -501,7 +503,7 @@ __device__ __forceinline__ u64 aid_hash(ulonglong2 k) {
 __device__ __forceinline__ bool keq(ulonglong2 a, ulonglong2 b) { return a.x == b.x && a.y == b.y; }
 
 #define TW_EMPTY 0ull
-#define TW_READY 1ull
+#define TW_READY OWGS_TW_READY
 #define TW_TOMB 2ull
 #define TW_CLAIM (1ull << 63)
 
@@ -602,7 +604,7 @@ __global__ __launch_bounds__(256) void owgs_act_fill_kernel(OwgsActTable T, cons
                                                             const int32_t* ticket, const int32_t* slot,
                                                             const uint8_t* state, int32_t* out_ticket,
                                                             uint8_t* out_existed, unsigned long long* counters,
-                                                            OwgsInflight F) {
+                                                            OwgsInflight F, OwgsArm A) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     int h = OWGS_NONE_V, mb = 0;
     bool bb = false;
@@ -624,6 +626,16 @@ __global__ __launch_bounds__(256) void owgs_act_fill_kernel(OwgsActTable T, cons
                 T.tk[s] = key[i];
                 T.tv[s] = make_int2(a, ticket[i]);
                 T.tn[s] = h;
+                // the item that creates the entry arms its timer (the by-name block of getOrElseUpdate, CLB:148-152)
+                long long d = OWGS_NO_DEADLINE;
+                if (A.inv) {
+                    const long long tl = A.tl[i];
+                    d = A.now + (tl > A.std_ms ? tl : A.std_ms) * A.factor + A.addon;  // CLB:103-105
+                    atomicMin(&T.tmin[s >> OWGS_TILE_LOG2], d);
+                }
+                T.td[s] = d;
+                T.ti[s] = A.inv ? A.inv[i] : -1;
+                T.tq[s] = A.seq_base + (u64)i;
                 out_existed[i] = 0;
                 out_ticket[i] = ticket[i];
                 atomicAdd(&counters[OWGS_CNT_INSERTED], 1ull);
@@ -742,7 +754,9 @@ __global__ __launch_bounds__(256) void owgs_ack_flags_kernel(int32_t n, const ui
     out_flags[i] = (uint8_t)(((info[i] >> 4) & 1) | (rel ? (rflags[i] & 3) << 1 : 0));
 }
 
-// rehash live entries into a fresh table (all keys distinct: plain CAS insertion); the namespace travels with the entry
+// rehash live entries into a fresh table (all keys distinct: plain CAS insertion); the namespace, the deadline, the
+// entry's invoker and the arm sequence travel with the entry, and the new table's deadline summary is built as arming
+// builds it
 __global__ __launch_bounds__(256) void owgs_act_rehash_kernel(OwgsActTable O, OwgsActTable T) {
     const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (s >= O.cap || O.tw[s] != TW_READY) return;
@@ -754,6 +768,11 @@ __global__ __launch_bounds__(256) void owgs_act_rehash_kernel(OwgsActTable O, Ow
             T.tk[t] = k;
             T.tv[t] = O.tv[s];
             T.tn[t] = O.tn[s];
+            const long long d = O.td[s];
+            T.td[t] = d;
+            T.ti[t] = O.ti[s];
+            T.tq[t] = O.tq[s];
+            if (d != OWGS_NO_DEADLINE) atomicMin(&T.tmin[t >> OWGS_TILE_LOG2], d);
             return;
         }
         t = (t + 1) & mask;
@@ -765,6 +784,7 @@ __global__ __launch_bounds__(256) void owgs_act_init_kernel(OwgsActTable T) {
     if (s >= T.cap) return;
     T.tw[s] = TW_EMPTY;
     T.owner[s] = 0x7FFFFFFF;
+    if ((s & (OWGS_TILE - 1)) == 0) T.tmin[s >> OWGS_TILE_LOG2] = OWGS_NO_DEADLINE;
 }
 
 // ------------------------------------------------------------------------------------------ launchers
@@ -796,11 +816,12 @@ extern "C" hipError_t owgs_launch_act_rehash(const OwgsActTable* O, const OwgsAc
 extern "C" hipError_t owgs_launch_act_track(const OwgsActTable* T, const ulonglong2* key, int32_t n,
                                             const int32_t* action, const int32_t* ns, const int32_t* ticket,
                                             int32_t* slot, uint8_t* state, int32_t* out_ticket, uint8_t* out_existed,
-                                            unsigned long long* counters, const OwgsInflight* F, hipStream_t st) {
+                                            unsigned long long* counters, const OwgsInflight* F, const OwgsArm* arm,
+                                            hipStream_t st) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(owgs_act_claim_kernel, GRID(n), *T, key, n, (const uint8_t*)nullptr, slot, state);
     hipLaunchKernelGGL(owgs_act_fill_kernel, GRID(n), *T, key, n, action, ns, ticket, slot, state, out_ticket,
-                       out_existed, counters, *F);
+                       out_existed, counters, *F, *arm);
     hipLaunchKernelGGL(owgs_act_publish_kernel, GRID(n), *T, n, slot, state);
     return hipGetLastError();
 }

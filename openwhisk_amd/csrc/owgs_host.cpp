@@ -66,7 +66,15 @@ extern "C" hipError_t owgs_launch_act_rehash(const OwgsActTable* O, const OwgsAc
 extern "C" hipError_t owgs_launch_act_track(const OwgsActTable* T, const ulonglong2* key, int32_t n,
                                             const int32_t* action, const int32_t* ns, const int32_t* ticket,
                                             int32_t* slot, uint8_t* state, int32_t* out_ticket, uint8_t* out_existed,
-                                            unsigned long long* counters, const OwgsInflight* F, hipStream_t st);
+                                            unsigned long long* counters, const OwgsInflight* F, const OwgsArm* arm,
+                                            hipStream_t st);
+extern "C" hipError_t owgs_launch_expire_scan(const OwgsExpireArgs* a, hipStream_t st);
+extern "C" size_t owgs_expire_sort_bytes(int32_t n);
+extern "C" hipError_t owgs_launch_expire_order(const OwgsExpireArgs* a, int32_t n, int32_t take, int32_t seq_bits,
+                                               void* temp, size_t temp_bytes, int32_t* idx0, int32_t* idx1,
+                                               unsigned long long* key, unsigned long long* key_s, ulonglong2* key_out,
+                                               int32_t* inst, uint8_t* info, long long* out_deadline, hipStream_t st);
+extern "C" hipError_t owgs_launch_deadline_min(const OwgsActTable* T, long long* out, hipStream_t st);
 extern "C" hipError_t owgs_launch_ns_gather(const int32_t* active, const int32_t* ns, int32_t n, int32_t* out,
                                             hipStream_t st);
 extern "C" size_t owgs_throttle_sort_bytes(int32_t n, int32_t bits);
@@ -301,6 +309,16 @@ struct owgs_ctx {
     DevBuf<int2> t_tv;
     DevBuf<int32_t> t_tn, t_owner;
     long long t_cap = 0, t_used = 0, t_live = 0;
+    // completion-ack timeouts (owgs_expire.hip): per-slot deadline / entry invoker / arm sequence, the per-tile summary,
+    // calculateCompletionAckTimeout's three settings (CLB:103-105), the arm-sequence counter, the sweep's scratch and
+    // its counters (owgs_expiry_stats)
+    DevBuf<long long> t_td, t_tmin, x_d, x_tl, x_outd;
+    DevBuf<int32_t> t_ti, x_slot, x_idx0, x_idx1, x_cnt, x_inv;
+    DevBuf<unsigned long long> t_tq, x_q, x_key, x_key_s;
+    DevBuf<uint8_t> x_temp;
+    long long a_std = 60000, a_factor = 2, a_addon = 60000;
+    unsigned long long arm_seq = 0;
+    long long x_sweeps = 0, x_tiles = 0, x_tiles_last = 0, x_expired = 0;
     // the in-flight books (CLB:62-65): namespace uuid -> dense handle, the per-namespace counters on the device
     // (int32, ns_cap entries, zero beyond the registered handles), the three totals on the host (folded in from each
     // call's counter words at the synchronisation the call ends with)
@@ -1860,6 +1878,13 @@ void owgs_destroy(owgs_ctx* c) {
     c->t_tv.release();
     c->t_tn.release();
     c->t_owner.release();
+    DevBuf<long long>* x64[] = {&c->t_td, &c->t_tmin, &c->x_d, &c->x_tl, &c->x_outd};
+    for (auto* b : x64) b->release();
+    DevBuf<int32_t>* x32[] = {&c->t_ti, &c->x_slot, &c->x_idx0, &c->x_idx1, &c->x_cnt, &c->x_inv};
+    for (auto* b : x32) b->release();
+    DevBuf<unsigned long long>* xu[] = {&c->t_tq, &c->x_q, &c->x_key, &c->x_key_s};
+    for (auto* b : xu) b->release();
+    c->x_temp.release();
     c->d_ns_active.release();
     c->q_key.release();
     c->q_idx0.release();
@@ -3589,6 +3614,10 @@ static OwgsActTable act_table(owgs_ctx* c) {
     T.tn = c->t_tn.p;
     T.owner = c->t_owner.p;
     T.cap = c->t_cap;
+    T.td = c->t_td.p;
+    T.ti = c->t_ti.p;
+    T.tq = c->t_tq.p;
+    T.tmin = c->t_tmin.p;
     return T;
 }
 
@@ -3602,13 +3631,19 @@ static int act_reserve(owgs_ctx* c, long long n) {
     DevBuf<unsigned long long> tw;
     DevBuf<ulonglong2> tk;
     DevBuf<int2> tv;
-    DevBuf<int32_t> tn, ow;
+    DevBuf<int32_t> tn, ow, ti;
+    DevBuf<long long> td, tmin;
+    DevBuf<unsigned long long> tq;
+    HIPCHK(c, td.reserve((size_t)cap));
+    HIPCHK(c, ti.reserve((size_t)cap));
+    HIPCHK(c, tq.reserve((size_t)cap));
+    HIPCHK(c, tmin.reserve((size_t)(cap >> OWGS_TILE_LOG2)));
     HIPCHK(c, tw.reserve((size_t)cap));
     HIPCHK(c, tk.reserve((size_t)cap));
     HIPCHK(c, tv.reserve((size_t)cap));
     HIPCHK(c, tn.reserve((size_t)cap));
     HIPCHK(c, ow.reserve((size_t)cap));
-    OwgsActTable T{tw.p, tk.p, tv.p, tn.p, ow.p, cap};
+    OwgsActTable T{tw.p, tk.p, tv.p, tn.p, ow.p, cap, td.p, ti.p, tq.p, tmin.p};
     HIPCHK(c, owgs_launch_act_init(&T, c->stream));
     if (c->t_cap > 0) {
         OwgsActTable O = act_table(c);
@@ -3620,6 +3655,18 @@ static int act_reserve(owgs_ctx* c, long long n) {
     c->t_tv.release();
     c->t_tn.release();
     c->t_owner.release();
+    c->t_td.release();
+    c->t_ti.release();
+    c->t_tq.release();
+    c->t_tmin.release();
+    c->t_td = td;
+    c->t_ti = ti;
+    c->t_tq = tq;
+    c->t_tmin = tmin;
+    td.p = nullptr;
+    ti.p = nullptr;
+    tq.p = nullptr;
+    tmin.p = nullptr;
     c->t_tw = tw;
     c->t_tk = tk;
     c->t_tv = tv;
@@ -3655,11 +3702,18 @@ static OwgsInflight inflight_args(owgs_ctx* c) {
     return F;
 }
 
-// ns = null: every item without a namespace (owgs_track_activations)
+// ns = null: every item without a namespace (owgs_track_activations); invoker = null: nothing armed (the untimed calls)
 static int track_impl(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* action, const int32_t* ns,
-                      const int32_t* ticket, int32_t* out_ticket, uint8_t* out_existed) {
+                      const int32_t* ticket, int32_t* out_ticket, uint8_t* out_existed,
+                      const int32_t* invoker = nullptr, const int64_t* time_limit_ms = nullptr, int64_t now_ms = 0) {
     if (!c || n < 0 || (n > 0 && (!aid32 || !action || !ticket || !out_ticket || !out_existed))) return OWGS_EINVAL;
     if (n == 0) return OWGS_OK;
+    if (invoker) {
+        if (now_ms < 0 || now_ms >= (1LL << 60)) return c->fail(OWGS_EINVAL, "track: now outside [0, 2^60)");
+        for (int32_t i = 0; i < n; ++i)
+            if (invoker[i] < 0 || time_limit_ms[i] < 0 || time_limit_ms[i] >= (1LL << 40))
+                return c->fail(OWGS_EINVAL, "track: negative invoker or time limit outside [0, 2^40)");
+    }
     if (!registered(c, n, action)) return c->fail(OWGS_ENOENT, "unknown action");
     if (ns) {
         const int32_t nn = (int32_t)c->ns_map.size();
@@ -3688,13 +3742,26 @@ static int track_impl(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* 
     HIPCHK(c, c->k_tick.reserve((size_t)n));
     HIPCHK(c, c->k_oflags.reserve((size_t)n));
     if (ns) HIPCHK(c, upload(c->k_r1, ns, (size_t)n, c->stream));
+    OwgsArm arm{};
+    arm.seq_base = c->arm_seq;
+    if (invoker) {
+        HIPCHK(c, upload(c->x_inv, invoker, (size_t)n, c->stream));
+        HIPCHK(c, upload(c->x_tl, (const long long*)time_limit_ms, (size_t)n, c->stream));
+        arm.inv = c->x_inv.p;
+        arm.tl = c->x_tl.p;
+        arm.now = now_ms;
+        arm.std_ms = c->a_std;
+        arm.factor = c->a_factor;
+        arm.addon = c->a_addon;
+    }
     HIPCHK(c, c->k_cnt.reserve(OWGS_CNT_WORDS));
     HIPCHK(c, hipMemsetAsync(c->k_cnt.p, 0, OWGS_CNT_WORDS * 8, c->stream));
     HIPCHK(c, owgs_launch_aid_decode(c->k_aid.p, n, nullptr, c->k_key.p, nullptr, nullptr, nullptr, c->stream));
     OwgsActTable T = act_table(c);
     const OwgsInflight F = inflight_args(c);
     HIPCHK(c, owgs_launch_act_track(&T, c->k_key.p, n, c->k_act.p, ns ? c->k_r1.p : nullptr, c->k_r0.p, c->k_slot.p,
-                                    c->k_state.p, c->k_tick.p, c->k_oflags.p, c->k_cnt.p, &F, c->stream));
+                                    c->k_state.p, c->k_tick.p, c->k_oflags.p, c->k_cnt.p, &F, &arm, c->stream));
+    c->arm_seq += (unsigned long long)n;  // arm order = track call order, then array index
     unsigned long long cnt[OWGS_CNT_WORDS];
     HIPCHK(c, hipMemcpyAsync(out_ticket, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(out_existed, c->k_oflags.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
@@ -3720,6 +3787,24 @@ int owgs_track_activations_ns(owgs_ctx* c, int32_t n, const char* aid32, const i
                               const int32_t* ticket, int32_t* out_ticket, uint8_t* out_existed) {
     if (n > 0 && !ns) return OWGS_EINVAL;
     return track_impl(c, n, aid32, action, ns, ticket, out_ticket, out_existed);
+}
+
+int owgs_set_ack_timeout(owgs_ctx* c, int64_t std_ms, int32_t factor, int64_t addon_ms) {
+    if (!c) return OWGS_EINVAL;
+    if (std_ms < 0 || std_ms >= (1LL << 40) || addon_ms < 0 || addon_ms >= (1LL << 40) || factor < 1 ||
+        factor >= (1 << 16))
+        return c->fail(OWGS_EINVAL, "ack timeout: std / addon outside [0, 2^40) or factor outside [1, 2^16)");
+    c->a_std = std_ms;
+    c->a_factor = factor;
+    c->a_addon = addon_ms;
+    return OWGS_OK;
+}
+
+int owgs_track_activations_timed(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* action, const int32_t* ns,
+                                 const int32_t* ticket, const int32_t* invoker, const int64_t* time_limit_ms,
+                                 int64_t now_ms, int32_t* out_ticket, uint8_t* out_existed) {
+    if (n > 0 && (!invoker || !time_limit_ms)) return OWGS_EINVAL;
+    return track_impl(c, n, aid32, action, ns, ticket, out_ticket, out_existed, invoker, time_limit_ms, now_ms);
 }
 
 // the completion's share of the books (CLB:280-284): one decrement per removed entry, the entries' megabytes
@@ -3912,6 +3997,128 @@ int owgs_complete_activations(owgs_ctx* c, int32_t n, const char* aid32, const i
     HIPCHK(c, hipMemcpy(out_kind, c->k_kind.p, (size_t)n, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(out_ticket, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(out_flags, c->k_oflags.p, (size_t)n, hipMemcpyDeviceToHost));
+    return OWGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------ completion-ack timeouts
+// owgs_expire.hip finds and orders the due entries; the removal, the books and releaseInvoker are ack_complete's.
+int owgs_expire_activations(owgs_ctx* c, int64_t now_ms, int32_t cap, int32_t feed_health, int32_t* out_n,
+                            int64_t* out_remaining, uint64_t* out_aid, int32_t* out_ticket, int32_t* out_invoker,
+                            int64_t* out_deadline, uint8_t* out_flags) {
+    if (!c || !out_n || !out_remaining || cap < 0 ||
+        (cap > 0 && (!out_aid || !out_ticket || !out_invoker || !out_deadline || !out_flags)))
+        return OWGS_EINVAL;
+    if (now_ms < 0 || now_ms >= (1LL << 60)) return c->fail(OWGS_EINVAL, "expire: now outside [0, 2^60)");
+    if (feed_health && now_ms < c->h_now)
+        return c->fail(OWGS_EINVAL, "expire: now before the health supervision's last batch");
+    OWGS_ENTER(c);
+    {
+        const int ro_ = order_on(c, c->stream);
+        if (ro_) return ro_;
+    }
+    hipStream_t st = c->stream;
+    if (c->t_cap == 0) {
+        int rc = act_reserve(c, 0);
+        if (rc) return rc;
+    }
+    // every buffer the sweep needs before its first kernel: the scan rewrites the summary words of the tiles it reads
+    // and the emit step completes them, so nothing between the two may fail for want of memory
+    const size_t live = (size_t)std::max<long long>(c->t_live, 1);
+    const size_t tb = owgs_expire_sort_bytes((int32_t)live);
+    HIPCHK(c, c->x_cnt.reserve(2));
+    HIPCHK(c, c->x_d.reserve(live));
+    HIPCHK(c, c->x_q.reserve(live));
+    HIPCHK(c, c->x_slot.reserve(live));
+    HIPCHK(c, c->x_idx0.reserve(live));
+    HIPCHK(c, c->x_idx1.reserve(live));
+    HIPCHK(c, c->x_key.reserve(live));
+    HIPCHK(c, c->x_key_s.reserve(live));
+    HIPCHK(c, c->x_outd.reserve(live));
+    HIPCHK(c, c->x_temp.reserve(tb));
+    HIPCHK(c, c->k_key.reserve(live));
+    HIPCHK(c, c->k_inst.reserve(live));
+    HIPCHK(c, c->k_info.reserve(live));
+    HIPCHK(c, c->k_kind.reserve(live));
+    HIPCHK(c, c->k_tick.reserve(live));
+    HIPCHK(c, c->k_oflags.reserve(live));
+    OwgsExpireArgs a{};
+    a.T = act_table(c);
+    a.now = now_ms;
+    a.cnt = c->x_cnt.p;
+    a.due_cap = (int32_t)live;
+    a.due_d = c->x_d.p;
+    a.due_q = c->x_q.p;
+    a.due_slot = c->x_slot.p;
+    HIPCHK(c, hipMemsetAsync(c->x_cnt.p, 0, 2 * sizeof(int32_t), st));
+    HIPCHK(c, owgs_launch_expire_scan(&a, st));
+    int32_t cnt[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(cnt, c->x_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->x_sweeps += 1;
+    c->x_tiles += cnt[1];
+    c->x_tiles_last = cnt[1];
+    const int32_t due = cnt[0];
+    if ((long long)due > c->t_live) return c->fail(OWGS_EDEVICE, "expire: more due entries than live ones");
+    const int32_t take = std::min(due, cap);
+    *out_n = take;
+    *out_remaining = (int64_t)due - take;
+    if (due == 0) return OWGS_OK;
+    int32_t seq_bits = 1;
+    while (seq_bits < 64 && (c->arm_seq >> seq_bits) != 0) ++seq_bits;
+    HIPCHK(c, owgs_launch_expire_order(&a, due, take, seq_bits, c->x_temp.p, tb, c->x_idx0.p, c->x_idx1.p, c->x_key.p,
+                                       c->x_key_s.p, c->k_key.p, c->k_inst.p, c->k_info.p, c->x_outd.p, st));
+    if (take == 0) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        return OWGS_OK;
+    }
+    // processCompletion(aid, tid, forced = true, isSystemError = false, invoker = entry.invoker) for each, in order
+    int rc = ack_complete(c, take, c->k_kind.p, c->k_tick.p, c->k_oflags.p, st);
+    if (rc) return rc;
+    c->x_expired += take;
+    HIPCHK(c, hipMemcpy(out_aid, c->k_key.p, (size_t)take * 16, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out_ticket, c->k_tick.p, (size_t)take * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out_invoker, c->k_inst.p, (size_t)take * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out_deadline, c->x_outd.p, (size_t)take * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out_flags, c->k_oflags.p, (size_t)take, hipMemcpyDeviceToHost));
+    if (!feed_health) return OWGS_OK;
+    // InvocationFinishedMessage(invoker, Timeout) of each expired entry (CLB:317) in the same order; ids the status
+    // vector cannot hold were never registered, and the pool ignores a message for an unregistered invoker
+    std::vector<int32_t> inv;
+    inv.reserve((size_t)take);
+    for (int32_t i = 0; i < take; ++i)
+        if (out_invoker[i] >= 0 && out_invoker[i] < OWGS_HEALTH_MAX_ID) inv.push_back(out_invoker[i]);
+    if (inv.empty()) return OWGS_OK;
+    const std::vector<uint8_t> kind(inv.size(), (uint8_t)OWGS_EV_TIMEOUT);
+    const std::vector<int64_t> t(inv.size(), now_ms), mem(inv.size(), 0);
+    return owgs_health_events(c, (int32_t)inv.size(), inv.data(), kind.data(), t.data(), mem.data(), now_ms, 0);
+}
+
+int owgs_next_deadline(owgs_ctx* c, int64_t* t_ms) {
+    if (!c || !t_ms) return OWGS_EINVAL;
+    *t_ms = INT64_MAX;
+    if (c->t_cap == 0) return OWGS_OK;
+    OWGS_ENTER(c);
+    {
+        const int ro_ = order_on(c, c->stream);
+        if (ro_) return ro_;
+    }
+    HIPCHK(c, c->x_outd.reserve(1));
+    const OwgsActTable T = act_table(c);
+    HIPCHK(c, owgs_launch_deadline_min(&T, c->x_outd.p, c->stream));
+    long long v = 0;
+    HIPCHK(c, hipMemcpyAsync(&v, c->x_outd.p, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *t_ms = (int64_t)v;
+    return OWGS_OK;
+}
+
+int owgs_expiry_stats(owgs_ctx* c, int64_t out[5]) {
+    if (!c || !out) return OWGS_EINVAL;
+    out[0] = c->x_sweeps;
+    out[1] = c->x_tiles;
+    out[2] = c->x_tiles_last;
+    out[3] = c->x_expired;
+    out[4] = c->t_cap >> OWGS_TILE_LOG2;
     return OWGS_OK;
 }
 

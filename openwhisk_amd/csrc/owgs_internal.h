@@ -567,6 +567,35 @@ struct OwgsActTable {
                                  // OWGS_NONE_V when it was tracked without one
     int32_t* owner;              // lowest batch index of a slot's inserts / removals (INT_MAX between calls)
     long long cap;
+    // completion-ack timeout of the entry (CLB:148-152; owgs_expire.hip), written by the lane that writes tk / tv / tn
+    long long* td;               // deadline in ms, OWGS_NO_DEADLINE = unarmed (tracked through an untimed call)
+    int32_t* ti;                 // ActivationEntry.invoker (CLB:158), -1 for an untimed entry
+    unsigned long long* tq;      // arm sequence: the host's counter at the track call + the batch index
+    long long* tmin;             // [cap / OWGS_TILE] tmin[t] <= min{ td[s] : s in tile t, tw[s] ready } at every call
+                                 // boundary; removals leave it alone (it may be stale-low), a sweep makes it exact
+};
+#define OWGS_TW_READY 1ull       // tw of a published entry
+#define OWGS_NO_DEADLINE 0x7FFFFFFFFFFFFFFFll
+#define OWGS_TILE_LOG2 10
+#define OWGS_TILE (1 << OWGS_TILE_LOG2)  // slots per word of the deadline summary (cap is a multiple: cap >= 65,536)
+
+// what a track call arms (owgs_track_activations_timed); inv == null: an untimed call, every deadline unarmed
+struct OwgsArm {
+    const int32_t* inv;          // [n] entry invoker
+    const long long* tl;         // [n] action time limit in ms
+    long long now, std_ms, factor, addon;  // deadline = now + max(tl, std_ms) * factor + addon (CLB:103-105)
+    unsigned long long seq_base; // arm sequence of batch index 0
+};
+
+// expiry sweep (owgs_expire.hip)
+struct OwgsExpireArgs {
+    OwgsActTable T;
+    long long now;
+    int32_t* cnt;                // [0] due entries found, [1] tiles scanned (zero before the scan)
+    int32_t due_cap;             // capacity of the due list (the host sizes it by the live entries)
+    long long* due_d;            // due list: deadline, arm sequence, slot (unordered)
+    unsigned long long* due_q;
+    int32_t* due_slot;
 };
 
 // The controller's in-flight books (CLB:62-65) as the track / completion kernels see them.  active = the dense
