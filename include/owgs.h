@@ -326,6 +326,61 @@ int owgs_activation_totals(owgs_ctx* ctx, int64_t out[3]);
 int owgs_throttle_batch(owgs_ctx* ctx, int32_t n, const int32_t* ns, const int32_t* limit, int32_t* out_count,
                         uint8_t* out_ok);
 
+/* ---- entitlement throttle gate (Entitlement.scala:197-202, 354-381) ----
+ * The two throttles every invoke and fire passes before publish, for a drained batch in array order: the per-minute
+ * rate throttle (invokeRateThrottler / triggerRateThrottler: RateThrottler.scala:47-54, RateInfo :60-86) and, only for
+ * an action that passed it, the concurrent throttle (ActivationThrottler.scala:41-49) over the in-flight books.
+ *
+ * State: per namespace handle two independent rate records (invoke, fire), each absent or (lastMin int64, count
+ * int32).  They persist across calls, grow with the namespace counters and, like the books, are left alone by
+ * owgs_snapshot / owgs_restore.
+ *
+ * Limit of an item: all three limits go through calculateIndividualLimit (Entitlement.scala:97-133, 144-149), with
+ * cs = the context's cluster size (owgs_update_cluster) at the time of the call:
+ *   abs   = override present ? override : system default
+ *   dil   = (int) ceil((double)abs * (cs > 1 ? 1.2 : 1.0))     IEEE double; the conversion saturates to int32
+ *   limit = dil == 0 ? 0 : max(dil / cs, 1)                     truncating division
+ * so a negative override yields 1.
+ *
+ * Item i with namespace h, kind, t_ms[i] (the System.currentTimeMillis of its check), m = t_ms[i] / 60000:
+ *   1. r = the record of (h, kind).  Absent: r = (m, 0).  m != r.lastMin: r = (m, 0) -- a clock that steps back
+ *      resets too (RateThrottler.scala:77-83).  Then r.count += 1 (wrapping int32), rate_count[i] = r.count,
+ *      rate_ok = rate_count[i] <= rate_limit[i].  The count is charged whether or not the item passes.
+ *   2. not rate_ok: verdict OWGS_ADMIT_RATE; the concurrent check is not evaluated, conc_count[i] = -1.
+ *   3. trigger: verdict OWGS_ADMIT_OK (no concurrent throttle, Entitlement.scala:378), conc_count[i] = -1,
+ *      conc_limit[i] = 0.
+ *   4. action: conc_count[i] = active[h] + #{ j < i : ns_j == h, verdict_j == OK, j an action };
+ *      verdict = conc_count[i] < conc_limit[i] ? OWGS_ADMIT_OK : OWGS_ADMIT_CONCURRENT.
+ * Step 4 is owgs_throttle_batch's rule restricted to the actions that passed the rate check, with its assumption (an
+ * admitted action is tracked afterwards); the in-flight counters are only read. */
+#define OWGS_ADMIT_OK 0
+#define OWGS_ADMIT_RATE 1
+#define OWGS_ADMIT_CONCURRENT 2
+#define OWGS_ADMIT_TRIGGER 1       /* kind bit 0: a trigger fire (else an action invoke) */
+#define OWGS_ADMIT_RATE_OVERRIDE 2 /* kind bit 1: rate_override[i] is limits.invocationsPerMinute / firesPerMinute */
+#define OWGS_ADMIT_CONC_OVERRIDE 4 /* kind bit 2: conc_override[i] is limits.concurrentInvocations */
+
+/* actionInvokePerMinuteLimit, triggerFirePerMinuteLimit, actionInvokeConcurrentLimit (Entitlement.scala:138, 142,
+ * 153).  Until set: 60, 60, 30.  Applies from the next owgs_admit_batch call. */
+int owgs_set_throttle_limits(owgs_ctx* ctx, int32_t invokes_per_minute, int32_t fires_per_minute,
+                             int32_t concurrent_invocations);
+
+/* The gate over n items.  An override array may be NULL when no item sets its kind bit.  t_ms in [0, 2^60).
+ * out_rate_limit / out_conc_limit are the computed limits (Messages.tooManyRequests(count, allowed); the
+ * ConcurrentInvocations metric is conc_count + 1, Entitlement.scala:389-391); out_conc_limit is written for every
+ * action, also when its concurrent check was skipped.  ns[i] = OWGS_NONE, a reserved kind bit, a kind bit without
+ * its array or a t_ms outside the range return OWGS_EINVAL, an unknown handle OWGS_ENOENT, all before any state
+ * changes. */
+int owgs_admit_batch(owgs_ctx* ctx, int32_t n, const int32_t* ns, const uint8_t* kind, const int64_t* t_ms,
+                     const int32_t* rate_override, const int32_t* conc_override, uint8_t* out_verdict,
+                     int32_t* out_rate_count, int32_t* out_rate_limit, int32_t* out_conc_count,
+                     int32_t* out_conc_limit);
+
+/* The rate records of n namespace handles: which = 0 the invoke throttler's, 1 the fire throttler's.  An absent record
+ * reads out_last_min = INT64_MIN, out_count = 0.  For tests and gauges; ordered after earlier calls. */
+int owgs_rate_state(owgs_ctx* ctx, int32_t n, const int32_t* ns, int32_t which, int64_t* out_last_min,
+                    int32_t* out_count);
+
 /* ---- completion-ack timeouts (CLB:103-105, 148-152) ----
  * setupActivation arms one timer per ActivationEntry inside getOrElseUpdate (CLB:148-152); a regular ack cancels it
  * (CLB:289); a fired timer runs processCompletion(aid, tid, forced = true, isSystemError = false, invoker =

@@ -25,6 +25,9 @@ HEALTHY, UNHEALTHY, UNRESPONSIVE, OFFLINE = 0, 1, 2, 3
 EV_PING, EV_SUCCESS, EV_SYSTEM_ERROR, EV_TIMEOUT, EV_STATE_TIMEOUT = range(5)
 NO_DEADLINE = 2**63 - 1  # owgs_next_deadline: nothing armed
 NS_INITIAL_CAP = 1024  # OWGS_NS_INITIAL_CAP: namespaces the device counter array holds before it first grows
+ADMIT_OK, ADMIT_RATE, ADMIT_CONCURRENT = 0, 1, 2  # owgs_admit_batch verdicts
+ADMIT_TRIGGER, ADMIT_RATE_OVERRIDE, ADMIT_CONC_OVERRIDE = 1, 2, 4  # ... and its kind bits
+RATE_ABSENT = -2**63  # owgs_rate_state: no record yet
 
 
 class OwgsError(RuntimeError):
@@ -133,6 +136,9 @@ def lib() -> C.CDLL:
         "owgs_active_activations": (C.c_int, [P, i32, P, P]),
         "owgs_activation_totals": (C.c_int, [P, P]),
         "owgs_throttle_batch": (C.c_int, [P, i32, P, P, P, P]),
+        "owgs_set_throttle_limits": (C.c_int, [P, i32, i32, i32]),
+        "owgs_admit_batch": (C.c_int, [P, i32, P, P, P, P, P, P, P, P, P, P]),
+        "owgs_rate_state": (C.c_int, [P, i32, P, i32, P, P]),
         "owgs_set_ack_timeout": (C.c_int, [P, C.c_int64, i32, C.c_int64]),
         "owgs_track_activations_timed": (C.c_int, [P, i32, P, P, P, P, P, P, C.c_int64, P, P]),
         "owgs_expire_activations": (C.c_int, [P, C.c_int64, i32, i32, P, P, P, P, P, P, P]),

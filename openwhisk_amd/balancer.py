@@ -342,6 +342,46 @@ class GpuShardingContainerPoolBalancer:
         self._chk(self._L.owgs_throttle_batch(self._h, n, _p(h if n else z), _p(lim if n else z), _p(cnt), _p(ok)))
         return cnt[:n], ok[:n]
 
+    def set_throttle_limits(self, invokes_per_minute: int = 60, fires_per_minute: int = 60,
+                            concurrent_invocations: int = 30):
+        """actionInvokePerMinuteLimit, triggerFirePerMinuteLimit, actionInvokeConcurrentLimit (Entitlement.scala:138,
+        142, 153): the system defaults of admit_batch, from its next call on."""
+        self._chk(self._L.owgs_set_throttle_limits(self._h, invokes_per_minute, fires_per_minute,
+                                                   concurrent_invocations))
+
+    def admit_batch(self, ns, kind, t_ms, rate_override=None, conc_override=None):
+        """The entitlement throttle gate over a drained batch in array order (owgs_admit_batch): the per-minute rate
+        throttle of each item's kind, then for an action that passed it the concurrent throttle.  kind: bit 0 trigger,
+        bit 1 rate_override[i] present, bit 2 conc_override[i] present; t_ms: the time of each check.  Returns
+        (verdict, rate_count, rate_limit, conc_count, conc_limit); conc_count is -1 where the concurrent check did not
+        run."""
+        h = np.ascontiguousarray(ns, dtype=np.int32)
+        kd = np.ascontiguousarray(kind, dtype=np.uint8)
+        t = np.ascontiguousarray(t_ms, dtype=np.int64)
+        n = len(h)
+        ro = None if rate_override is None else np.ascontiguousarray(rate_override, dtype=np.int32)
+        co = None if conc_override is None else np.ascontiguousarray(conc_override, dtype=np.int32)
+        if any(len(a) != n for a in (kd, t, ro, co) if a is not None):
+            raise ValueError("kind, t_ms and the overrides need one value per item")
+        verdict = np.zeros(max(n, 1), dtype=np.uint8)
+        out = np.zeros((4, max(n, 1)), dtype=np.int32)
+        z = np.zeros(1, np.int64)
+        self._chk(self._L.owgs_admit_batch(
+            self._h, n, _p(h if n else z), _p(kd if n else z), _p(t if n else z),
+            None if ro is None else _p(ro if n else z), None if co is None else _p(co if n else z),
+            _p(verdict), _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3])))
+        return verdict[:n], out[0, :n], out[1, :n], out[2, :n], out[3, :n]
+
+    def rate_state(self, ns, which: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """The RateInfo records (lastMin, count) of namespace handles: which = 0 the invoke throttler's, 1 the fire
+        throttler's; (_lib.RATE_ABSENT, 0) for a namespace it never checked."""
+        h = np.ascontiguousarray(ns, dtype=np.int32)
+        n = len(h)
+        last = np.zeros(max(n, 1), dtype=np.int64)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._L.owgs_rate_state(self._h, n, _p(h if n else np.zeros(1, np.int32)), which, _p(last), _p(cnt)))
+        return last[:n], cnt[:n]
+
     def process_acks(self, msgs):
         """processAcknowledgement (CLB:205-232) for raw ack messages (bytes): (kind, invoker, ticket, flags)."""
         n = len(msgs)

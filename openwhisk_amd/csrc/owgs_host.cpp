@@ -82,6 +82,14 @@ extern "C" hipError_t owgs_launch_throttle(const int32_t* ns, const int32_t* lim
                                            void* temp, size_t temp_bytes, int32_t* key_out, int32_t* idx_in,
                                            int32_t* idx_out, const int32_t* active, int32_t* out_count,
                                            uint8_t* out_ok, hipStream_t st);
+extern "C" hipError_t owgs_launch_admit(const int32_t* ns, int32_t bits, void* temp, size_t temp_bytes,
+                                        int32_t* key_out, int32_t* idx_in, int32_t* idx_out, const OwgsAdmitArgs* args,
+                                        hipStream_t st);
+extern "C" hipError_t owgs_launch_rate_gather(const long long* rate_min, const int32_t* rate_cnt, int32_t ns_cap,
+                                              int32_t which, const int32_t* ns, int32_t n, long long* out_min,
+                                              int32_t* out_cnt, hipStream_t st);
+extern "C" hipError_t owgs_launch_rate_grow(const long long* old_min, const int32_t* old_cnt, int32_t old_cap,
+                                            long long* new_min, int32_t* new_cnt, int32_t new_cap, hipStream_t st);
 extern "C" hipError_t owgs_launch_ack_complete(const OwgsActTable* T, const OwgsAckCompleteArgs* a, hipStream_t st);
 extern "C" hipError_t owgs_launch_ack_flags(int32_t n, const uint8_t* info, const uint8_t* rflags,
                                             const uint8_t* out_kind, uint8_t* out_flags, hipStream_t st);
@@ -326,6 +334,15 @@ struct owgs_ctx {
     DevBuf<int32_t> d_ns_active, q_key, q_idx0, q_idx1;
     DevBuf<uint8_t> q_temp;
     int32_t ns_cap = 0;
+    // the entitlement throttle gate (owgs_admit_batch): the RateInfo records of the two rate throttlers, entry
+    // which * ns_cap + handle (lastMin OWGS_RATE_ABSENT, count 0: never checked), grown with d_ns_active; the three
+    // system defaults (Entitlement.scala:138, 142, 153; ansible/group_vars/all:73-75); its output block on the device
+    // ([4 n] int32 then [n] verdict bytes) and the pinned host block it is read back into with one copy
+    DevBuf<long long> d_rate_min, g_min;
+    DevBuf<int32_t> d_rate_cnt, g_out;
+    void* g_pin = nullptr;
+    size_t g_pin_bytes = 0;
+    int32_t lim_invoke = 60, lim_fire = 60, lim_conc = 30;
     long long f_total = 0, f_mb_managed = 0, f_mb_blackbox = 0;
     long long health_ms = 0;
     DevBuf<ulonglong2> k_key;
@@ -1886,6 +1903,12 @@ void owgs_destroy(owgs_ctx* c) {
     for (auto* b : xu) b->release();
     c->x_temp.release();
     c->d_ns_active.release();
+    c->d_rate_min.release();
+    c->d_rate_cnt.release();
+    c->g_min.release();
+    c->g_out.release();
+    if (c->g_pin) (void)hipHostFree(c->g_pin);
+    c->g_pin = nullptr;
     c->q_key.release();
     c->q_idx0.release();
     c->q_idx1.release();
@@ -4148,18 +4171,29 @@ int owgs_register_namespaces(owgs_ctx* c, int32_t n, const uint64_t* uuid128, in
         }
         int64_t cap = std::max<int64_t>(c->ns_cap, OWGS_NS_INITIAL_CAP);
         while (cap < need) cap *= 2;
-        DevBuf<int32_t> nb;
-        HIPCHK(c, nb.reserve((size_t)cap));
-        hipError_t e = hipMemsetAsync(nb.p, 0, (size_t)cap * 4, c->stream);
+        DevBuf<int32_t> nb, rc;
+        DevBuf<long long> rm;  // the rate records grow with the counters: old records copied, new handles absent
+        hipError_t e = nb.reserve((size_t)cap);
+        if (e == hipSuccess) e = rm.reserve(2 * (size_t)cap);
+        if (e == hipSuccess) e = rc.reserve(2 * (size_t)cap);
+        if (e == hipSuccess) e = hipMemsetAsync(nb.p, 0, (size_t)cap * 4, c->stream);
         if (e == hipSuccess && c->ns_cap > 0)
             e = hipMemcpyAsync(nb.p, c->d_ns_active.p, (size_t)c->ns_cap * 4, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (the old array is freed below)
+        if (e == hipSuccess)
+            e = owgs_launch_rate_grow(c->d_rate_min.p, c->d_rate_cnt.p, c->ns_cap, rm.p, rc.p, (int32_t)cap, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (the old arrays are freed below)
         if (e != hipSuccess) {
             nb.release();
+            rm.release();
+            rc.release();
             return c->fail(OWGS_EDEVICE, "namespace counters", e);
         }
         c->d_ns_active.release();
         c->d_ns_active = nb;
+        c->d_rate_min.release();
+        c->d_rate_min = rm;
+        c->d_rate_cnt.release();
+        c->d_rate_cnt = rc;
         c->ns_cap = (int32_t)cap;
     }
     for (const auto& kv : fresh) c->ns_map[kv.first] = kv.second;
@@ -4229,6 +4263,120 @@ int owgs_throttle_batch(owgs_ctx* c, int32_t n, const int32_t* ns, const int32_t
                                    c->q_idx1.p, c->d_ns_active.p, c->k_tick.p, c->k_oflags.p, c->stream));
     HIPCHK(c, hipMemcpyAsync(out_count, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(out_ok, c->k_oflags.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return OWGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------ entitlement throttle gate
+// checkUserThrottle + checkConcurrentUserThrottle (Entitlement.scala:197-202, 354-381) for a drained batch; the
+// semantics are in include/owgs.h, the kernel in owgs_inflight.hip.
+int owgs_set_throttle_limits(owgs_ctx* c, int32_t invokes_per_minute, int32_t fires_per_minute,
+                             int32_t concurrent_invocations) {
+    if (!c) return OWGS_EINVAL;
+    c->lim_invoke = invokes_per_minute;
+    c->lim_fire = fires_per_minute;
+    c->lim_conc = concurrent_invocations;
+    return OWGS_OK;
+}
+
+int owgs_admit_batch(owgs_ctx* c, int32_t n, const int32_t* ns, const uint8_t* kind, const int64_t* t_ms,
+                     const int32_t* rate_override, const int32_t* conc_override, uint8_t* out_verdict,
+                     int32_t* out_rate_count, int32_t* out_rate_limit, int32_t* out_conc_count,
+                     int32_t* out_conc_limit) {
+    if (!c || n < 0 ||
+        (n > 0 && (!ns || !kind || !t_ms || !out_verdict || !out_rate_count || !out_rate_limit || !out_conc_count ||
+                   !out_conc_limit)))
+        return OWGS_EINVAL;
+    if (n == 0) return OWGS_OK;
+    // argument contract: validated before any state changes
+    for (int32_t i = 0; i < n; ++i) {
+        if (ns[i] == OWGS_NONE) return c->fail(OWGS_EINVAL, "throttle gate without a namespace");
+        if (kind[i] & ~(OWGS_ADMIT_TRIGGER | OWGS_ADMIT_RATE_OVERRIDE | OWGS_ADMIT_CONC_OVERRIDE))
+            return c->fail(OWGS_EINVAL, "throttle gate: reserved kind bits");
+        if (((kind[i] & OWGS_ADMIT_RATE_OVERRIDE) && !rate_override) ||
+            ((kind[i] & OWGS_ADMIT_CONC_OVERRIDE) && !conc_override))
+            return c->fail(OWGS_EINVAL, "throttle gate: an override bit without its array");
+        if (t_ms[i] < 0 || t_ms[i] >= (1LL << 60)) return c->fail(OWGS_EINVAL, "throttle gate: time outside [0, 2^60)");
+    }
+    if (!ns_known(c, n, ns)) return c->fail(OWGS_ENOENT, "unknown namespace");
+    OWGS_ENTER(c);
+    {
+        const int ro_ = order_on(c, c->stream);
+        if (ro_) return ro_;
+    }
+    int32_t bits = 1;
+    while (((int64_t)1 << bits) < (int64_t)c->ns_map.size()) ++bits;
+    const size_t tb = owgs_throttle_sort_bytes(n, bits);
+    const size_t N = (size_t)n;
+    HIPCHK(c, c->q_temp.reserve(tb));
+    HIPCHK(c, c->q_key.reserve(N));
+    HIPCHK(c, c->q_idx0.reserve(N));
+    HIPCHK(c, c->q_idx1.reserve(N));
+    HIPCHK(c, upload(c->k_act, ns, N, c->stream));
+    HIPCHK(c, upload(c->k_kind, kind, N, c->stream));
+    HIPCHK(c, upload(c->k_off, t_ms, N, c->stream));
+    if (rate_override) HIPCHK(c, upload(c->k_r0, rate_override, N, c->stream));
+    if (conc_override) HIPCHK(c, upload(c->k_r1, conc_override, N, c->stream));
+    const size_t out_bytes = 17 * N;
+    HIPCHK(c, c->g_out.reserve(4 * N + (N + 3) / 4));
+    if (c->g_pin_bytes < out_bytes) {
+        if (c->g_pin) (void)hipHostFree(c->g_pin);
+        c->g_pin = nullptr;
+        c->g_pin_bytes = 0;
+        HIPCHK(c, hipHostMalloc(&c->g_pin, out_bytes * 2, hipHostMallocDefault));
+        c->g_pin_bytes = out_bytes * 2;
+    }
+    OwgsAdmitArgs A{};
+    A.n = n;
+    A.kind = c->k_kind.p;
+    A.t_ms = c->k_off.p;
+    A.rate_ov = rate_override ? c->k_r0.p : nullptr;
+    A.conc_ov = conc_override ? c->k_r1.p : nullptr;
+    A.def_invoke = c->lim_invoke;
+    A.def_fire = c->lim_fire;
+    A.def_conc = c->lim_conc;
+    A.cluster = c->cluster;  // loadBalancer.clusterSize (SCPB:254)
+    A.active = c->d_ns_active.p;
+    A.rate_min = c->d_rate_min.p;
+    A.rate_cnt = c->d_rate_cnt.p;
+    A.ns_cap = c->ns_cap;
+    A.out_verdict = (uint8_t*)(c->g_out.p + 4 * N);
+    A.out_rate_count = c->g_out.p;
+    A.out_rate_limit = c->g_out.p + N;
+    A.out_conc_count = c->g_out.p + 2 * N;
+    A.out_conc_limit = c->g_out.p + 3 * N;
+    HIPCHK(c, owgs_launch_admit(c->k_act.p, bits, c->q_temp.p, tb, c->q_key.p, c->q_idx0.p, c->q_idx1.p, &A,
+                                c->stream));
+    // the five outputs come back with one copy into pinned memory (five copies into the caller's pageable arrays
+    // cost the call 55-71 us more) and are handed out on the host
+    HIPCHK(c, hipMemcpyAsync(c->g_pin, c->g_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const char* HO = (const char*)c->g_pin;
+    memcpy(out_rate_count, HO, 4 * N);
+    memcpy(out_rate_limit, HO + 4 * N, 4 * N);
+    memcpy(out_conc_count, HO + 8 * N, 4 * N);
+    memcpy(out_conc_limit, HO + 12 * N, 4 * N);
+    memcpy(out_verdict, HO + 16 * N, N);
+    return OWGS_OK;
+}
+
+int owgs_rate_state(owgs_ctx* c, int32_t n, const int32_t* ns, int32_t which, int64_t* out_last_min,
+                    int32_t* out_count) {
+    if (!c || n < 0 || which < 0 || which > 1 || (n > 0 && (!ns || !out_last_min || !out_count))) return OWGS_EINVAL;
+    if (n == 0) return OWGS_OK;
+    if (!ns_known(c, n, ns)) return c->fail(OWGS_ENOENT, "unknown namespace");
+    OWGS_ENTER(c);
+    {
+        const int ro_ = order_on(c, c->stream);
+        if (ro_) return ro_;
+    }
+    HIPCHK(c, upload(c->k_act, ns, (size_t)n, c->stream));
+    HIPCHK(c, c->g_min.reserve((size_t)n));
+    HIPCHK(c, c->k_tick.reserve((size_t)n));
+    HIPCHK(c, owgs_launch_rate_gather(c->d_rate_min.p, c->d_rate_cnt.p, c->ns_cap, which, c->k_act.p, n, c->g_min.p,
+                                      c->k_tick.p, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_last_min, c->g_min.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_count, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return OWGS_OK;
 }

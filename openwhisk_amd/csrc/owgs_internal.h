@@ -631,6 +631,29 @@ struct OwgsAckCompleteArgs {
     OwgsInflight fl;
 };
 
+// The entitlement throttle gate (owgs_admit_resolve_kernel, owgs_inflight.hip); every pointer is device memory.
+// rate_min / rate_cnt hold the two RateInfo records of every namespace handle: entry which * ns_cap + handle, which =
+// 0 invokeRateThrottler, 1 triggerRateThrottler; lastMin = OWGS_RATE_ABSENT (with count 0) while the namespace has
+// never been checked by that throttler.
+#define OWGS_RATE_ABSENT ((long long)(-9223372036854775807LL - 1))
+struct OwgsAdmitArgs {
+    const uint32_t* key;         // the batch's namespace handles, sorted (stable)
+    const int32_t* idx;          // batch index of each sorted position
+    int32_t n;
+    const uint8_t* kind;         // by batch index: bit0 trigger, bit1 rate override, bit2 concurrent override
+    const int64_t* t_ms;
+    const int32_t* rate_ov;      // null when no item sets bit1
+    const int32_t* conc_ov;      // null when no item sets bit2
+    int32_t def_invoke, def_fire, def_conc;
+    int32_t cluster;             // loadBalancer.clusterSize (>= 1)
+    const int32_t* active;
+    long long* rate_min;
+    int32_t* rate_cnt;
+    int32_t ns_cap;
+    uint8_t* out_verdict;
+    int32_t *out_rate_count, *out_rate_limit, *out_conc_count, *out_conc_limit;
+};
+
 // ActivationMessage serialisation + topic fan-out (owgs_msgs.hip); every pointer is device memory
 struct OwgsMsgArgs {
     int32_t n;
