@@ -461,6 +461,65 @@ int owgs_health_events(owgs_ctx* ctx, int32_t n, const int32_t* invoker, const u
 int owgs_health_read(owgs_ctx* ctx, int32_t cap, int32_t* n, uint8_t* status, int64_t* user_memory_bytes,
                      int32_t* test_actions, uint32_t* ring, int64_t* next_tick);
 
+/* ---- supervision feeds: raw pings and ack results drive the FSM ----
+ * The two inputs of the health FSM without a host detour.  The events are built on the device from what the ping
+ * parser / the completion path left there, in array order (mailbox order), and go through the batch launch of
+ * owgs_health_events; no event array is uploaded.
+ *
+ * out_summary (all three calls): [0] events fed; [1] entries of the status vector (below its new size) whose stored
+ * state or userMemory differs from before the call, entries the vector grew by included; [2] test actions this batch
+ * sent (the sum of owgs_health_read's test_actions).  The shim reads the vectors only when [1] or [2] is non-zero.
+ * apply: 0 hands nothing to owgs_update_invokers; 1 hands the status vector over as owgs_health_events does; 2 hands
+ * it over only if out_summary[1] > 0 -- the reference sends CurrentInvokerPoolState only on CurrentState / Transition
+ * (ISUP:139-149), and updateInvokers with an unchanged vector changes nothing (SCPB:512-551).  apply = 2 compares
+ * with the vector before THIS call: a caller that mixes it with apply = 0 calls hands over late. */
+
+/* Per-message outcome of owgs_process_pings (out_kind): */
+#define OWGS_PING_FAIL 0        /* PingMessage.parse fails (ISUP:181-183): the shim logs the raw message */
+#define OWGS_PING_UNSUPPORTED 2 /* outside the device parser's limits (the list of OWGS_ACK_UNSUPPORTED): JVM parses */
+#define OWGS_PING_FED 3         /* parsed; fed to the FSM as OWGS_EV_PING at t_ms[i] */
+#define OWGS_PING_RANGE 4       /* parsed, instance outside [0, OWGS_HEALTH_MAX_ID): reported, not fed */
+
+/* Replaces: InvokerPool.processInvokerPing (ISUP:174-185) for n raw messages of the `health` topic (UTF-8 bytes,
+ * offsets off[0..n]) received at t_ms[i]: PingMessage.parse (Message.scala:261-268) on the device, then
+ * `self ! p` for every parsed ping (ISUP:120-131).
+ * Parse: the whole message must be valid JSON as spray-json 1.3.5 reads it (the scanner and limits of
+ * owgs_process_acks).  The root must be an object; the last top-level member whose decoded name is "name" is the
+ * InvokerInstanceId (jsonFormat4, InstanceId.scala:31-49), read exactly as the `invoker` member of an ack: instance a
+ * JSON number through BigDecimal.intValue; uniqueName / displayedName absent, null or a string; userMemory a string
+ * matching (?i)\s?(\d+)\s?(GB|MB|KB|B|G|M|K)\s? with \d = [0-9], \s = [ \t\n\x0B\f\r] and digits that fit a Long
+ * (Size.scala:119-138).  A non-object root or no "name" member is OWGS_PING_FAIL.
+ * out_user_memory_bytes = size * {1, 2^10, 2^20, 2^30} in wrapping int64 arithmetic (ByteSize.toBytes, Size.scala:
+ * 28-62, 166-172): what the shim passes to updateInvokers.  out_instance is written for FED and RANGE; every other
+ * output of a message that is not FED is 0.
+ * Feed: the FED messages, in array order, are OWGS_EV_PING events (instance, t_ms[i], bytes); the rest drop out.  The
+ * time contract is owgs_health_events': t_ms non-decreasing and not before the previous batch's now_ms, now_ms not
+ * before the last t_ms, all in [0, 2^60) -- checked over all n entries, whatever they parse to, before anything runs;
+ * a violation is OWGS_EINVAL with no state change.  Timers due up to now_ms fire also when nothing is FED.
+ * A negative instance makes the reference's actor throw (status(-1), ISUP:125); here it is OWGS_PING_RANGE, as is an
+ * instance the dense status vector does not accept.  An UNSUPPORTED ping the JVM parses itself reaches the FSM later,
+ * through owgs_health_events at the JVM's current time. */
+int owgs_process_pings(owgs_ctx* ctx, int32_t n, const char* bytes, const int64_t* off, const int64_t* t_ms,
+                       int64_t now_ms, int32_t apply, uint8_t* out_kind, int32_t* out_instance,
+                       int64_t* out_user_memory_bytes, int32_t out_summary[3]);
+
+/* owgs_process_acks / owgs_complete_activations -- outcomes, outputs, releases and books exactly theirs -- followed by
+ * `invokerPool ! InvocationFinishedMessage(invoker, result)` (CLB:317, 327) on the device: for each item in array
+ * order whose outcome is OWGS_ACK_RELEASED or OWGS_ACK_HEALTH and whose invoker is in [0, OWGS_HEALTH_MAX_ID) one
+ * event at time now_ms: OWGS_EV_TIMEOUT if forced (owgs_complete_activations_supervised, flag bit 0), else
+ * OWGS_EV_SYSTEM_ERROR if isSystemError, else OWGS_EV_SUCCESS (CLB:266-276).  The invoker is the call's / the
+ * message's (CLB:317, 327), not the entry's.  NOENTRY, FORCED_NOENTRY, FAIL, JVM and UNSUPPORTED feed nothing
+ * (CLB:328-345); an id without an actor is ignored by the FSM as by InvokerPool (ISUP:135-137).  now_ms before the
+ * FSM's last now_ms or outside [0, 2^60) is OWGS_EINVAL before any ack is processed.  A batch that feeds no event
+ * leaves the FSM's clock alone, as the expiry sweep does.  Messages reported OWGS_ACK_JVM are completed by the shim
+ * through owgs_complete_activations_supervised once the JVM has parsed them. */
+int owgs_process_acks_supervised(owgs_ctx* ctx, int32_t n, const char* bytes, const int64_t* off, uint8_t* out_kind,
+                                 int32_t* out_invoker, int32_t* out_ticket, uint8_t* out_flags, int64_t now_ms,
+                                 int32_t apply, int32_t out_summary[3]);
+int owgs_complete_activations_supervised(owgs_ctx* ctx, int32_t n, const char* aid32, const int32_t* invoker,
+                                         const uint8_t* flags, uint8_t* out_kind, int32_t* out_ticket,
+                                         uint8_t* out_flags, int64_t now_ms, int32_t apply, int32_t out_summary[3]);
+
 /* ---- ActivationMessage serialisation + per-invoker topic fan-out ----
  * Replaces: ActivationMessage.serialize (jsonFormat11 + spray-json compactPrint, Message.scala:51-70, 170-175) and
  * the per-activation producer.send to topic "invoker<N>" (sendActivationToInvoker, CommonLoadBalancer.scala:175-198)

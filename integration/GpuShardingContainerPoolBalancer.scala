@@ -69,6 +69,25 @@ object OwgsNative {
                                 outDeadline: Array[Long], outFlags: Array[Byte]): Int
   /** owgs_next_deadline: a lower bound of the earliest armed deadline (Long.MaxValue: none; negative: an error) */
   @native def nextDeadline(ctx: Long): Long
+  /** owgs_process_pings: the raw messages of one `health` feed batch with their receive times; PingMessage.parse and
+   *  the FSM's ping events run on the device (InvokerPool.processInvokerPing, ISUP:174-185).  outKind: 0 parse failure
+   *  (log the raw message), 2 left to the JVM parser, 3 fed, 4 parsed with an instance the FSM does not take.
+   *  outSummary: events fed, status entries changed, test actions to send; apply 0 / 1 / 2 = never / always / only on
+   *  a change hand the status vector to updateInvokers. */
+  @native def processPings(ctx: Long, bytes: Array[Byte], off: Array[Long], tMs: Array[Long], n: Int, nowMs: Long,
+                           apply: Int, outKind: Array[Byte], outInstance: Array[Int], outUserMemory: Array[Long],
+                           outSummary: Array[Int]): Int
+  /** owgs_process_acks_supervised: one ack feed batch; the InvocationFinishedMessage of every RELEASED / HEALTH
+   *  outcome (CLB:317, 327) reaches the FSM on the device at nowMs. */
+  @native def processAcksSupervised(ctx: Long, bytes: Array[Byte], off: Array[Long], n: Int, outKind: Array[Byte],
+                                    outInvoker: Array[Int], outTicket: Array[Int], outFlags: Array[Byte],
+                                    nowMs: Long, apply: Int, outSummary: Array[Int]): Int
+  /** owgs_complete_activations_supervised: processCompletion called directly (flags bit0 forced, bit1 isSystemError,
+   *  bit2 health transid), e.g. for the messages processAcksSupervised left to the JVM (outKind 1), results fed. */
+  @native def completeActivationsSupervised(ctx: Long, aid32: Array[Byte], invokers: Array[Int], flags: Array[Byte],
+                                            n: Int, outKind: Array[Byte], outTicket: Array[Int],
+                                            outFlags: Array[Byte], nowMs: Long, apply: Int,
+                                            outSummary: Array[Int]): Int
   @native def lastError(ctx: Long): String
 }
 

@@ -352,6 +352,111 @@ JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00
     return rc == OWGS_OK ? n : rc;
 }
 
+/* ---- supervision feeds: the bytes of the `health` and ack topics drive the FSM on the device ----
+ * outSummary[0] events fed, [1] status entries changed, [2] test actions to send: the shim calls healthRead only when
+ * [1] or [2] is non-zero.  apply 0 / 1 / 2: never / always / only on a change hand the vector to updateInvokers. */
+static int offsets_fit(const int64_t* po, jint n, jlong nb) {
+    for (jint i = 0; i < n; ++i)
+        if (po[i] < 0 || po[i + 1] < po[i] || po[i + 1] > nb) return 0;
+    return 1;
+}
+
+/* raw pings of one feed batch with their receive times (InvokerPool.processInvokerPing, ISUP:174-185) */
+JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_processPings(
+    JNIEnv* env, jobject self, jlong h, jbyteArray bytes, jlongArray off, jlongArray tMs, jint n, jlong nowMs,
+    jint apply, jbyteArray outKind, jintArray outInstance, jlongArray outUserMemory, jintArray outSummary) {
+    if (!bytes || !off || !tMs || !outKind || !outInstance || !outUserMemory || !outSummary ||
+        !n_fits(env, n, tMs, outKind, outInstance, outUserMemory) || !n_fits(env, (jlong)n + 1, off, NULL, NULL, NULL) ||
+        !n_fits(env, 3, outSummary, NULL, NULL, NULL))
+        return OWGS_EINVAL;
+    int64_t* po = jcopy_in(env, off, (jlong)n + 1, 8, 'J');
+    if (!po) return OWGS_ENOMEM;
+    const jlong nb = (*env)->GetArrayLength(env, bytes);
+    if (!offsets_fit(po, n, nb)) {
+        free(po);
+        return OWGS_EINVAL;
+    }
+    char* pb = jcopy_in(env, bytes, nb, 1, 'B');
+    int64_t* pt = jcopy_in(env, tMs, n, 8, 'J');
+    uint8_t* pk = calloc((size_t)(n > 0 ? n : 1), 1);
+    int32_t* pi = calloc((size_t)(n > 0 ? n : 1), 4);
+    int64_t* pm = calloc((size_t)(n > 0 ? n : 1), 8);
+    int32_t summary[3] = {0, 0, 0};
+    int rc = OWGS_ENOMEM;
+    if (pb && pt && pk && pi && pm) rc = owgs_process_pings(CTX(h), n, pb, po, pt, nowMs, apply, pk, pi, pm, summary);
+    if (rc == OWGS_OK) {
+        jcopy_out(env, outKind, n, pk, 'B');
+        jcopy_out(env, outInstance, n, pi, 'I');
+        jcopy_out(env, outUserMemory, n, pm, 'J');
+        jcopy_out(env, outSummary, 3, summary, 'I');
+    }
+    FREE_ALL(po, pb, pt, pk, pi, pm);
+    return rc;
+}
+
+/* processAcks, then the RELEASED / HEALTH outcomes' InvocationFinishedMessage to the FSM at nowMs (CLB:317, 327) */
+JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_processAcksSupervised(
+    JNIEnv* env, jobject self, jlong h, jbyteArray bytes, jlongArray off, jint n, jbyteArray outKind,
+    jintArray outInvoker, jintArray outTicket, jbyteArray outFlags, jlong nowMs, jint apply, jintArray outSummary) {
+    if (!bytes || !off || !outKind || !outInvoker || !outTicket || !outFlags || !outSummary ||
+        !n_fits(env, n, outKind, outInvoker, outTicket, outFlags) ||
+        !n_fits(env, (jlong)n + 1, off, NULL, NULL, NULL) || !n_fits(env, 3, outSummary, NULL, NULL, NULL))
+        return OWGS_EINVAL;
+    int64_t* po = jcopy_in(env, off, (jlong)n + 1, 8, 'J');
+    if (!po) return OWGS_ENOMEM;
+    const jlong nb = (*env)->GetArrayLength(env, bytes);
+    if (!offsets_fit(po, n, nb)) {
+        free(po);
+        return OWGS_EINVAL;
+    }
+    char* pb = jcopy_in(env, bytes, nb, 1, 'B');
+    uint8_t* pk = calloc((size_t)(n > 0 ? n : 1), 1);
+    int32_t* pi = calloc((size_t)(n > 0 ? n : 1), 4);
+    int32_t* pt = calloc((size_t)(n > 0 ? n : 1), 4);
+    uint8_t* pf = calloc((size_t)(n > 0 ? n : 1), 1);
+    int32_t summary[3] = {0, 0, 0};
+    int rc = OWGS_ENOMEM;
+    if (pb && pk && pi && pt && pf)
+        rc = owgs_process_acks_supervised(CTX(h), n, pb, po, pk, pi, pt, pf, nowMs, apply, summary);
+    if (rc == OWGS_OK) {
+        jcopy_out(env, outKind, n, pk, 'B');
+        jcopy_out(env, outInvoker, n, pi, 'I');
+        jcopy_out(env, outTicket, n, pt, 'I');
+        jcopy_out(env, outFlags, n, pf, 'B');
+        jcopy_out(env, outSummary, 3, summary, 'I');
+    }
+    FREE_ALL(po, pb, pk, pi, pt, pf);
+    return rc;
+}
+
+/* completeActivations (timeouts the shim keeps itself, OWGS_ACK_JVM messages), then the results to the FSM */
+JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_completeActivationsSupervised(
+    JNIEnv* env, jobject self, jlong h, jbyteArray aid32, jintArray invokers, jbyteArray flags, jint n,
+    jbyteArray outKind, jintArray outTicket, jbyteArray outFlags, jlong nowMs, jint apply, jintArray outSummary) {
+    if (!aid32 || !invokers || !flags || !outKind || !outTicket || !outFlags || !outSummary ||
+        !n_fits(env, n, invokers, flags, outKind, outTicket) || !n_fits(env, n, outFlags, NULL, NULL, NULL) ||
+        !n_fits(env, 32LL * n, aid32, NULL, NULL, NULL) || !n_fits(env, 3, outSummary, NULL, NULL, NULL))
+        return OWGS_EINVAL;
+    char* pa = jcopy_in(env, aid32, 32LL * n, 1, 'B');
+    int32_t* pi = jcopy_in(env, invokers, n, 4, 'I');
+    uint8_t* pc = jcopy_in(env, flags, n, 1, 'B');
+    uint8_t* pk = calloc((size_t)(n > 0 ? n : 1), 1);
+    int32_t* pt = calloc((size_t)(n > 0 ? n : 1), 4);
+    uint8_t* pf = calloc((size_t)(n > 0 ? n : 1), 1);
+    int32_t summary[3] = {0, 0, 0};
+    int rc = OWGS_ENOMEM;
+    if (pa && pi && pc && pk && pt && pf)
+        rc = owgs_complete_activations_supervised(CTX(h), n, pa, pi, pc, pk, pt, pf, nowMs, apply, summary);
+    if (rc == OWGS_OK) {
+        jcopy_out(env, outKind, n, pk, 'B');
+        jcopy_out(env, outTicket, n, pt, 'I');
+        jcopy_out(env, outFlags, n, pf, 'B');
+        jcopy_out(env, outSummary, 3, summary, 'I');
+    }
+    FREE_ALL(pa, pi, pc, pk, pt, pf);
+    return rc;
+}
+
 /* ---- ActivationMessage serialisation + topic fan-out ---- */
 JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_registerTemplates(
     JNIEnv* env, jobject self, jlong h, jbyteArray a, jlongArray aOff, jbyteArray b, jlongArray bOff, jint n) {

@@ -23,6 +23,8 @@ REL_NOSUCHELEMENT, REL_OVERFLOW, REL_NOENTRY = 1, 2, 4
 ACK_FAIL, ACK_JVM, ACK_UNSUPPORTED, ACK_RELEASED, ACK_HEALTH, ACK_NOENTRY, ACK_FORCED_NOENTRY = range(7)
 HEALTHY, UNHEALTHY, UNRESPONSIVE, OFFLINE = 0, 1, 2, 3
 EV_PING, EV_SUCCESS, EV_SYSTEM_ERROR, EV_TIMEOUT, EV_STATE_TIMEOUT = range(5)
+PING_FAIL, PING_UNSUPPORTED, PING_FED, PING_RANGE = 0, 2, 3, 4  # owgs_process_pings outcomes
+HEALTH_MAX_ID = 1 << 24  # OWGS_HEALTH_MAX_ID
 NO_DEADLINE = 2**63 - 1  # owgs_next_deadline: nothing armed
 NS_INITIAL_CAP = 1024  # OWGS_NS_INITIAL_CAP: namespaces the device counter array holds before it first grows
 ADMIT_OK, ADMIT_RATE, ADMIT_CONCURRENT = 0, 1, 2  # owgs_admit_batch verdicts
@@ -109,6 +111,9 @@ def lib() -> C.CDLL:
         "owgs_serialize_activations": (C.c_int, [P, P, i32, P, C.c_int64, P, P, P, P, P]),
         "owgs_serialize_activations_device": (C.c_int, [P, P, i32, P, C.c_int64, P, P, P, P, P, P]),
         "owgs_health_read": (C.c_int, [P, i32, P, P, P, P, P, P]),
+        "owgs_process_pings": (C.c_int, [P, i32, P, P, P, C.c_int64, i32, P, P, P, P]),
+        "owgs_process_acks_supervised": (C.c_int, [P, i32, P, P, P, P, P, P, C.c_int64, i32, P]),
+        "owgs_complete_activations_supervised": (C.c_int, [P, i32, P, P, P, P, P, P, C.c_int64, i32, P]),
         "owgs_register_actions": (C.c_int, [P, i32, P, P, P, P, P, P, P, P, P, P, P]),
         "owgs_publish_batch": (C.c_int, [P, i32, P, P, u64, P, P]),
         "owgs_release_batch": (C.c_int, [P, i32, P, P, P]),

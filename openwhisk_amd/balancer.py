@@ -411,6 +411,63 @@ class GpuShardingContainerPoolBalancer:
         self._chk(self._L.owgs_complete_activations(self._h, n, _p(buf), _p(inv), _p(f), _p(kind), _p(tk), _p(fl)))
         return kind[:n], tk[:n], fl[:n]
 
+    # ------------------------------------------------------------------ supervision feeds (ISUP:174-185, CLB:317, 327)
+    def process_pings(self, msgs, t_ms, now_ms: int, apply: int = 0):
+        """processInvokerPing (ISUP:174-185) for raw `health`-topic messages received at t_ms: PingMessage.parse on the
+        device, the parsed pings fed to the health FSM in order.  apply 0 / 1 / 2: never / always / only on a change
+        hand the status vector to updateInvokers.  (kind, instance, userMemory bytes, summary) with summary =
+        (events fed, status entries changed, test actions sent)."""
+        n = len(msgs)
+        t = np.ascontiguousarray(t_ms, dtype=np.int64)
+        if len(t) != n:
+            raise ValueError("process_pings: one time per message")
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m) for m in msgs])
+        buf = np.frombuffer(b"".join(msgs) + b"\0", dtype=np.uint8)
+        kind = np.zeros(max(n, 1), dtype=np.uint8)
+        inst = np.zeros(max(n, 1), dtype=np.int32)
+        mem = np.zeros(max(n, 1), dtype=np.int64)
+        summ = np.zeros(3, dtype=np.int32)
+        self._chk(self._L.owgs_process_pings(self._h, n, _p(buf), _p(off), _p(t if n else np.zeros(1, np.int64)),
+                                             int(now_ms), int(apply), _p(kind), _p(inst), _p(mem), _p(summ)))
+        return kind[:n], inst[:n], mem[:n], tuple(int(x) for x in summ)
+
+    def process_acks_supervised(self, msgs, now_ms: int, apply: int = 0):
+        """process_acks, then InvocationFinishedMessage of every RELEASED / HEALTH outcome to the health FSM at now_ms
+        (CLB:266-276, 317, 327) without leaving the device: (kind, invoker, ticket, flags, summary)."""
+        n = len(msgs)
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m) for m in msgs])
+        buf = np.frombuffer(b"".join(msgs) + b"\0", dtype=np.uint8)
+        kind = np.zeros(max(n, 1), dtype=np.uint8)
+        inv = np.zeros(max(n, 1), dtype=np.int32)
+        tk = np.zeros(max(n, 1), dtype=np.int32)
+        fl = np.zeros(max(n, 1), dtype=np.uint8)
+        summ = np.zeros(3, dtype=np.int32)
+        self._chk(self._L.owgs_process_acks_supervised(self._h, n, _p(buf), _p(off), _p(kind), _p(inv), _p(tk), _p(fl),
+                                                       int(now_ms), int(apply), _p(summ)))
+        return kind[:n], inv[:n], tk[:n], fl[:n], tuple(int(x) for x in summ)
+
+    def complete_activations_supervised(self, aids, invokers, now_ms: int, apply: int = 0, forced=None,
+                                        system_error=None, health=None):
+        """complete_activations, then the results to the health FSM at now_ms (forced: Timeout, CLB:266-267):
+        (kind, ticket, flags, summary)."""
+        n = len(aids)
+        buf = np.frombuffer(b"".join(a.encode("ascii") for a in aids) or b"\0", dtype=np.uint8)
+        inv = np.ascontiguousarray(invokers if n else np.zeros(1), dtype=np.int32)
+        z = np.zeros(n, dtype=np.uint8)
+        f = ((np.asarray(forced if forced is not None else z, dtype=np.uint8) & 1)
+             | (np.asarray(system_error if system_error is not None else z, dtype=np.uint8) & 1) << 1
+             | (np.asarray(health if health is not None else z, dtype=np.uint8) & 1) << 2).astype(np.uint8)
+        f = np.ascontiguousarray(f if n else np.zeros(1, np.uint8))
+        kind = np.zeros(max(n, 1), dtype=np.uint8)
+        tk = np.zeros(max(n, 1), dtype=np.int32)
+        fl = np.zeros(max(n, 1), dtype=np.uint8)
+        summ = np.zeros(3, dtype=np.int32)
+        self._chk(self._L.owgs_complete_activations_supervised(self._h, n, _p(buf), _p(inv), _p(f), _p(kind), _p(tk),
+                                                               _p(fl), int(now_ms), int(apply), _p(summ)))
+        return kind[:n], tk[:n], fl[:n], tuple(int(x) for x in summ)
+
     def activations_live(self) -> int:
         v = C.c_int64()
         self._chk(self._L.owgs_activations_live(self._h, C.byref(v)))

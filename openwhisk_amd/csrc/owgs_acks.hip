@@ -91,9 +91,10 @@ __device__ __forceinline__ int unit_at(Win& W, int64_t& i) {
 #define K_UNIQUE 6
 #define K_DISPLAYED 7
 #define K_USERMEM 8
-__constant__ char k_names[9][16] = {"activationId", "invoker", "isSystemError", "response", "transid",
-                                    "instance",     "uniqueName", "displayedName", "userMemory"};
-__constant__ int k_len[9] = {12, 7, 13, 8, 7, 8, 10, 13, 10};
+#define K_NAME 9
+__constant__ char k_names[10][16] = {"activationId", "invoker", "isSystemError", "response", "transid",
+                                     "instance",     "uniqueName", "displayedName", "userMemory", "name"};
+__constant__ int k_len[10] = {12, 7, 13, 8, 7, 8, 10, 13, 10, 4};
 
 // bitmask of the candidate names (lo..hi) the decoded key equals
 __device__ __forceinline__ int key_match(Win& W, int64_t k, int lo, int hi) {
@@ -228,10 +229,11 @@ __device__ __forceinline__ int64_t skip_value(Win& W, int64_t i) {
     }
 }
 
-// ByteSize.fromString over the decoded string at a (Size.scala:119-138)
-__device__ __forceinline__ bool bytesize_ok(Win& W, int64_t a) {
+// ByteSize.fromString over the decoded string at a (Size.scala:119-138); *bytes = toBytes (Size.scala:28-62: size times
+// 1, 2^10, 2^20 or 2^30 in wrapping Long arithmetic)
+__device__ __forceinline__ bool bytesize(Win& W, int64_t a, long long* bytes) {
     int64_t i = a + 1;
-    int st = 0;
+    int st = 0, sh = 0;
     u64 val = 0;
     bool ovf = false;
     for (;;) {
@@ -249,18 +251,146 @@ __device__ __forceinline__ bool bytesize_ok(Win& W, int64_t a) {
                     if (val > (u64)(0x7FFFFFFFFFFFFFFFull - (u64)(u - '0')) / 10ull) ovf = true;
                     else val = val * 10ull + (u64)(u - '0');
                 } else st = ws ? 3 : gmk ? 4 : U == 'B' ? 5 : 9;
+                if (gmk) sh = U == 'K' ? 10 : U == 'M' ? 20 : 30;
                 break;
-            case 3: st = gmk ? 4 : U == 'B' ? 5 : 9; break;
+            case 3:
+                st = gmk ? 4 : U == 'B' ? 5 : 9;
+                if (gmk) sh = U == 'K' ? 10 : U == 'M' ? 20 : 30;
+                break;
             case 4: st = U == 'B' ? 5 : ws ? 6 : 9; break;
             case 5: st = ws ? 6 : 9; break;
             default: st = 9;
         }
         if (st == 9) return false;
     }
+    *bytes = (long long)(val << sh);
     return (st == 4 || st == 5 || st == 6) && !ovf;
 }
 
 __device__ __forceinline__ bool num_start(int c) { return c == '-' || (c >= '0' && c <= '9'); }
+
+// U+FFFF (EF BF BF) reads as spray-json's end-of-input marker: left to the JVM
+__device__ __forceinline__ bool has_ffff(Win& W, int64_t b, int64_t e) {
+    bool ffff = false;
+    for (int64_t i = b; i + 2 < e && !ffff; ++i)
+        ffff = W.at(i) == 0xEF && W.at(i + 1) == 0xBF && W.at(i + 2) == 0xBF;
+    return ffff;
+}
+
+// The whole message [b, e) against the grammar; v[q] = where the value of the LAST top-level member named
+// k_names[LO + q] starts (-1: no such member), top_obj = the root is an object.  0, EV_ERR or EV_UNSUP.
+template <int LO, int HI>
+__device__ __forceinline__ int scan_message(Win& W, int64_t b, int64_t e, int64_t (&v)[HI - LO + 1], bool& top_obj) {
+    u64 stk = 0;  // bit d-1: container at depth d is an object
+    int d = 0, ev = 0;
+    int64_t i = b;
+    while (is_ws(W.at(i))) ++i;
+    top_obj = W.at(i) == '{';
+    enum { VALUE, KEY, AFTER } st = VALUE;
+    for (;;) {
+        if (st == VALUE) {
+            const int c = W.at(i);
+            if (c == '{' || c == '[') {
+                if (d == 64) { ev = EV_UNSUP; break; }
+                stk = (stk & ~(1ull << d)) | ((u64)(c == '{') << d);
+                ++d;
+                ++i;
+                while (is_ws(W.at(i))) ++i;
+                const int c2 = W.at(i);
+                if (c2 == (c == '{' ? '}' : ']')) { --d; ++i; st = AFTER; }
+                else st = c == '{' ? KEY : VALUE;
+                continue;
+            }
+            int64_t j;
+            if (c == '"') j = scan_string(W, i);
+            else if (num_start(c)) j = scan_number(W, i);
+            else if (c == 't') j = (W.at(i + 1) == 'r' && W.at(i + 2) == 'u' && W.at(i + 3) == 'e') ? i + 4 : -1;
+            else if (c == 'f') j = (W.at(i + 1) == 'a' && W.at(i + 2) == 'l' && W.at(i + 3) == 's' && W.at(i + 4) == 'e') ? i + 5 : -1;
+            else if (c == 'n') j = (W.at(i + 1) == 'u' && W.at(i + 2) == 'l' && W.at(i + 3) == 'l') ? i + 4 : -1;
+            else j = -1;
+            if (j == -2) { ev = EV_UNSUP; break; }
+            if (j < 0) { ev = EV_ERR; break; }
+            i = j;
+            st = AFTER;
+        } else if (st == KEY) {
+            if (W.at(i) != '"') { ev = EV_ERR; break; }
+            const int64_t k = i;
+            i = scan_string(W, i);
+            if (i < 0) { ev = EV_ERR; break; }
+            while (is_ws(W.at(i))) ++i;
+            if (W.at(i) != ':') { ev = EV_ERR; break; }
+            ++i;
+            while (is_ws(W.at(i))) ++i;
+            if (d == 1) {
+                const int id = key_match(W, k, LO, HI);
+#pragma unroll
+                for (int q = 0; q <= HI - LO; ++q)  // constant indices: v stays in registers (no scratch)
+                    if (id - LO == q) v[q] = i;
+            }
+            st = VALUE;
+        } else {  // AFTER a value
+            while (is_ws(W.at(i))) ++i;
+            if (d == 0) {
+                if (i != e) ev = EV_ERR;
+                break;
+            }
+            const int c = W.at(i);
+            const bool obj = (stk >> (d - 1)) & 1ull;
+            if (c == ',') {
+                ++i;
+                while (is_ws(W.at(i))) ++i;
+                st = obj ? KEY : VALUE;
+            } else if (c == (obj ? '}' : ']')) {
+                --d;
+                ++i;
+            } else {
+                ev = EV_ERR;
+                break;
+            }
+        }
+    }
+    return ev;
+}
+
+// InvokerInstanceId (jsonFormat4, InstanceId.scala:31-49) from the validated value at a: instance through
+// BigDecimal.intValue, uniqueName / displayedName as Option[String], userMemory through ByteSize.fromString, its
+// toBytes in mem.  Sets fail (deserializationError) / unsup (beyond the parser's limits), never clears them.
+__device__ __forceinline__ void instance_id(Win& W, int64_t a, int& inst, long long& mem, bool& fail, bool& unsup) {
+    mem = 0;
+    if (W.at(a) != '{') fail = true;
+    else {
+        int64_t w[4] = {-1, -1, -1, -1};
+        int64_t j = a + 1;
+        while (is_ws(W.at(j))) ++j;
+        if (W.at(j) != '}') {
+            for (;;) {
+                while (is_ws(W.at(j))) ++j;
+                const int64_t k = j;
+                j = scan_string(W, j);
+                while (is_ws(W.at(j))) ++j;
+                ++j;  // ':'
+                while (is_ws(W.at(j))) ++j;
+                const int id = key_match(W, k, K_INSTANCE, K_USERMEM);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)  // constant indices: w stays in registers
+                    if (id - K_INSTANCE == q) w[q] = j;
+                j = skip_value(W, j);
+                while (is_ws(W.at(j))) ++j;
+                if (W.at(j) != ',') break;
+                ++j;
+            }
+        }
+        if (w[0] < 0 || !num_start(W.at(w[0]))) fail = true;
+        else {
+            int sg;
+            inst = (int32_t)(uint32_t)number_bits(W, w[0], &sg);
+            if (sg > 34) unsup = true;
+        }
+        for (int q = 1; q <= 2; ++q)
+            if (w[q] >= 0 && W.at(w[q]) != '"' && W.at(w[q]) != 'n') fail = true;
+        if (w[3] < 0 || W.at(w[3]) != '"' || !bytesize(W, w[3], &mem)) fail = true;
+    }
+}
 
 __global__ __launch_bounds__(256) void owgs_ack_parse_kernel(OwgsAckParseArgs A) {
     const int m = blockIdx.x * 256 + threadIdx.x;
@@ -269,83 +399,13 @@ __global__ __launch_bounds__(256) void owgs_ack_parse_kernel(OwgsAckParseArgs A)
     Win W(A.bytes, b, e);
     int kind = OWGS_ACK_FAIL, inst = -1, sys = 0, health = 0;
     u64 hi = 0, lo = 0;
-    // U+FFFF (EF BF BF) reads as spray-json's end-of-input marker: left to the JVM
-    bool ffff = false;
-    for (int64_t i = b; i + 2 < e && !ffff; ++i)
-        ffff = W.at(i) == 0xEF && W.at(i + 1) == 0xBF && W.at(i + 2) == 0xBF;
-    if (ffff) {
+    if (has_ffff(W, b, e)) {
         kind = OWGS_ACK_UNSUPPORTED;
     } else {
         // ---------------------------------------------------------------- phase 1: grammar, top-level members
-        u64 stk = 0;  // bit d-1: container at depth d is an object
-        int d = 0, ev = 0;
         int64_t v[5] = {-1, -1, -1, -1, -1};
-        int64_t i = b;
-        while (is_ws(W.at(i))) ++i;
-        const bool top_obj = W.at(i) == '{';
-        enum { VALUE, KEY, AFTER } st = VALUE;
-        for (;;) {
-            if (st == VALUE) {
-                const int c = W.at(i);
-                if (c == '{' || c == '[') {
-                    if (d == 64) { ev = EV_UNSUP; break; }
-                    stk = (stk & ~(1ull << d)) | ((u64)(c == '{') << d);
-                    ++d;
-                    ++i;
-                    while (is_ws(W.at(i))) ++i;
-                    const int c2 = W.at(i);
-                    if (c2 == (c == '{' ? '}' : ']')) { --d; ++i; st = AFTER; }
-                    else st = c == '{' ? KEY : VALUE;
-                    continue;
-                }
-                int64_t j;
-                if (c == '"') j = scan_string(W, i);
-                else if (num_start(c)) j = scan_number(W, i);
-                else if (c == 't') j = (W.at(i + 1) == 'r' && W.at(i + 2) == 'u' && W.at(i + 3) == 'e') ? i + 4 : -1;
-                else if (c == 'f') j = (W.at(i + 1) == 'a' && W.at(i + 2) == 'l' && W.at(i + 3) == 's' && W.at(i + 4) == 'e') ? i + 5 : -1;
-                else if (c == 'n') j = (W.at(i + 1) == 'u' && W.at(i + 2) == 'l' && W.at(i + 3) == 'l') ? i + 4 : -1;
-                else j = -1;
-                if (j == -2) { ev = EV_UNSUP; break; }
-                if (j < 0) { ev = EV_ERR; break; }
-                i = j;
-                st = AFTER;
-            } else if (st == KEY) {
-                if (W.at(i) != '"') { ev = EV_ERR; break; }
-                const int64_t k = i;
-                i = scan_string(W, i);
-                if (i < 0) { ev = EV_ERR; break; }
-                while (is_ws(W.at(i))) ++i;
-                if (W.at(i) != ':') { ev = EV_ERR; break; }
-                ++i;
-                while (is_ws(W.at(i))) ++i;
-                if (d == 1) {
-                    const int id = key_match(W, k, K_AID, K_TID);
-#pragma unroll
-                    for (int q = 0; q < 5; ++q)  // constant indices: v stays in registers (no scratch)
-                        if (id == q) v[q] = i;
-                }
-                st = VALUE;
-            } else {  // AFTER a value
-                while (is_ws(W.at(i))) ++i;
-                if (d == 0) {
-                    if (i != e) ev = EV_ERR;
-                    break;
-                }
-                const int c = W.at(i);
-                const bool obj = (stk >> (d - 1)) & 1ull;
-                if (c == ',') {
-                    ++i;
-                    while (is_ws(W.at(i))) ++i;
-                    st = obj ? KEY : VALUE;
-                } else if (c == (obj ? '}' : ']')) {
-                    --d;
-                    ++i;
-                } else {
-                    ev = EV_ERR;
-                    break;
-                }
-            }
-        }
+        bool top_obj;
+        const int ev = scan_message<K_AID, K_TID>(W, b, e, v, top_obj);
         if (ev == EV_UNSUP) kind = OWGS_ACK_UNSUPPORTED;
         else if (ev == EV_ERR || !top_obj) kind = OWGS_ACK_FAIL;
         else if (v[K_RESP] >= 0) kind = OWGS_ACK_JVM;
@@ -384,40 +444,8 @@ __global__ __launch_bounds__(256) void owgs_ack_parse_kernel(OwgsAckParseArgs A)
                 else if (c != 'f' && c != 'n') fail = true;
             }
             {
-                const int64_t a = v[K_INV];
-                if (W.at(a) != '{') fail = true;
-                else {
-                    int64_t w[4] = {-1, -1, -1, -1};
-                    int64_t j = a + 1;
-                    while (is_ws(W.at(j))) ++j;
-                    if (W.at(j) != '}') {
-                        for (;;) {
-                            while (is_ws(W.at(j))) ++j;
-                            const int64_t k = j;
-                            j = scan_string(W, j);
-                            while (is_ws(W.at(j))) ++j;
-                            ++j;  // ':'
-                            while (is_ws(W.at(j))) ++j;
-                            const int id = key_match(W, k, K_INSTANCE, K_USERMEM);
-#pragma unroll
-                            for (int q = 0; q < 4; ++q)  // constant indices: w stays in registers
-                                if (id - K_INSTANCE == q) w[q] = j;
-                            j = skip_value(W, j);
-                            while (is_ws(W.at(j))) ++j;
-                            if (W.at(j) != ',') break;
-                            ++j;
-                        }
-                    }
-                    if (w[0] < 0 || !num_start(W.at(w[0]))) fail = true;
-                    else {
-                        int sg;
-                        inst = (int32_t)(uint32_t)number_bits(W, w[0], &sg);
-                        if (sg > 34) unsup = true;
-                    }
-                    for (int q = 1; q <= 2; ++q)
-                        if (w[q] >= 0 && W.at(w[q]) != '"' && W.at(w[q]) != 'n') fail = true;
-                    if (w[3] < 0 || W.at(w[3]) != '"' || !bytesize_ok(W, w[3])) fail = true;
-                }
+                long long mem;
+                instance_id(W, v[K_INV], inst, mem, fail, unsup);
             }
             if (v[K_TID] >= 0 && W.at(v[K_TID]) == '[') {
                 int64_t el[3] = {-1, -1, -1};
@@ -465,6 +493,40 @@ __global__ __launch_bounds__(256) void owgs_ack_parse_kernel(OwgsAckParseArgs A)
     A.key[m] = make_ulonglong2(hi, lo);
     A.inst[m] = inst;
     A.info[m] = (uint8_t)(kind | (sys << 4) | (health << 5) | (A.forced ? (A.forced[m] & 1) << 6 : 0));
+}
+
+// PingMessage.parse (Message.scala:261-268: jsonFormat(PingMessage.apply _, "name")) for the raw messages of the
+// `health` topic (InvokerPool.processInvokerPing, ISUP:174-185), one thread per message: the scanner and the
+// InvokerInstanceId conversion of the ack parser above, with its limits.  kind = OWGS_PING_*; instance for FED / RANGE,
+// userMemory.toBytes for FED, 0 otherwise.
+__global__ __launch_bounds__(256) void owgs_ping_parse_kernel(const uint8_t* bytes, const int64_t* off, int32_t n,
+                                                              uint8_t* out_kind, int32_t* out_inst,
+                                                              long long* out_mem) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= n) return;
+    const int64_t b = off[m], e = off[m + 1];
+    Win W(bytes, b, e);
+    int kind = OWGS_PING_FAIL, inst = 0;
+    long long mem = 0;
+    if (has_ffff(W, b, e)) {
+        kind = OWGS_PING_UNSUPPORTED;
+    } else {
+        int64_t v[1] = {-1};
+        bool top_obj;
+        const int ev = scan_message<K_NAME, K_NAME>(W, b, e, v, top_obj);
+        if (ev == EV_UNSUP) kind = OWGS_PING_UNSUPPORTED;
+        else if (ev == EV_ERR || !top_obj || v[0] < 0) kind = OWGS_PING_FAIL;
+        else {
+            bool fail = false, unsup = false;
+            instance_id(W, v[0], inst, mem, fail, unsup);
+            kind = fail ? OWGS_PING_FAIL
+                        : unsup ? OWGS_PING_UNSUPPORTED
+                                : (inst >= 0 && inst < OWGS_HEALTH_MAX_ID_V) ? OWGS_PING_FED : OWGS_PING_RANGE;
+        }
+    }
+    out_kind[m] = (uint8_t)kind;
+    out_inst[m] = (kind == OWGS_PING_FED || kind == OWGS_PING_RANGE) ? inst : 0;
+    out_mem[m] = kind == OWGS_PING_FED ? mem : 0;
 }
 
 // 32 hex chars per id (caller-side ActivationId strings) -> 128-bit keys; ids that are not 32 x [0-9a-f] get
@@ -793,6 +855,13 @@ __global__ __launch_bounds__(256) void owgs_act_init_kernel(OwgsActTable T) {
 extern "C" hipError_t owgs_launch_ack_parse(const OwgsAckParseArgs* a, hipStream_t st) {
     if (a->n <= 0) return hipSuccess;
     hipLaunchKernelGGL(owgs_ack_parse_kernel, GRID(a->n), *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t owgs_launch_ping_parse(const uint8_t* bytes, const int64_t* off, int32_t n, uint8_t* out_kind,
+                                             int32_t* out_inst, long long* out_mem, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(owgs_ping_parse_kernel, GRID(n), bytes, off, n, out_kind, out_inst, out_mem);
     return hipGetLastError();
 }
 

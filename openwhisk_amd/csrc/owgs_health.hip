@@ -20,7 +20,9 @@
 //                                                  padded each new status entry (its userMemory)
 //   owgs_health_fsm_kernel                         one lane per invoker: its events in order, due timers between
 //                                                  them and up to `now` (akka FSM rules restated in the header of
-//                                                  oracle/owhealth_oracle.c, which the parity tests compare with)
+//                                                  oracle/owhealth_oracle.c, which the parity tests compare with);
+//                                                  optionally counts the entries it changed and the test actions
+//                                                  it sent (the supervision feeds' summary, owgs_feeds.hip)
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -65,6 +67,7 @@ struct HealthArgs {
     const int32_t* pad_src;
     int32_t old_size, new_size;
     int64_t now;
+    int32_t* sum;  // null, or two words the FSM kernel adds to: entries changed, test actions sent
 };
 
 struct Inv {
@@ -199,16 +202,17 @@ __global__ __launch_bounds__(1024) void owgs_health_padmin_kernel(const int32_t*
     }
 }
 
-__global__ __launch_bounds__(256) void owgs_health_fsm_kernel(HealthArgs A) {
-    const int32_t k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= A.new_size) return;
+// one invoker's batch; chg = its stored state byte or userMemory differs from before, nt = test actions it sent
+__device__ __forceinline__ void fsm_lane(const HealthArgs& A, int32_t k, int& chg, int& nt) {
     Inv a;
     a.st = A.st[k];
+    const int st0 = a.st;
     a.ring = A.ring[k];
     a.last = A.last[k];
     a.tick = A.tick[k];
     a.tests = 0;
     int64_t mem = A.mem[k];
+    const int64_t mem0 = mem;
     if (a.st == H_ABSENT) {  // inside the new status vector: padded by the registration that grew it past k
         const int32_t src = A.pad_src[k];
         if (src != NO_EVENT) {
@@ -259,6 +263,23 @@ __global__ __launch_bounds__(256) void owgs_health_fsm_kernel(HealthArgs A) {
     A.tick[k] = a.tick;
     A.mem[k] = mem;
     A.tests[k] = a.tests;
+    chg = a.st != st0 || mem != mem0;
+    nt = a.tests;
+}
+
+// sum[0] += entries that changed, sum[1] += test actions sent (both skipped when sum is null): a wave ballot / a wave
+// sum, one atomic per wave and word
+__global__ __launch_bounds__(256) void owgs_health_fsm_kernel(HealthArgs A) {
+    const int32_t k = blockIdx.x * 256 + threadIdx.x;
+    int chg = 0, nt = 0;
+    if (k < A.new_size) fsm_lane(A, k, chg, nt);
+    if (!A.sum) return;
+    const int nc = __popcll(__ballot(chg));
+    for (int o = 32; o; o >>= 1) nt += __shfl_xor(nt, o);
+    if ((threadIdx.x & 63) == 0) {
+        if (nc) atomicAdd(&A.sum[0], nc);
+        if (nt) atomicAdd(&A.sum[1], nt);
+    }
 }
 
 #define GRID(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256), 0, st
@@ -285,7 +306,8 @@ extern "C" hipError_t owgs_launch_health_batch(const int32_t* ev_inv, const uint
                                                int32_t* idx_out, int64_t* packed, int32_t* seg_beg, int32_t* seg_end,
                                                int32_t* reg_first, int32_t* pad_src, uint8_t* s, uint32_t* ring,
                                                int64_t* last, int64_t* tick, int64_t* mem, int32_t* tests,
-                                               int32_t old_size, int32_t new_size, int64_t now, hipStream_t st) {
+                                               int32_t old_size, int32_t new_size, int64_t now, int32_t* sum,
+                                               hipStream_t st) {
     hipError_t e;
     if (new_size <= 0) return hipSuccess;
     e = hipMemsetAsync(seg_beg, 0, (size_t)new_size * 4, st);
@@ -321,6 +343,7 @@ extern "C" hipError_t owgs_launch_health_batch(const int32_t* ev_inv, const uint
     A.old_size = old_size;
     A.new_size = new_size;
     A.now = now;
+    A.sum = sum;
     hipLaunchKernelGGL(owgs_health_regfirst_kernel, GRID(new_size), A);
     hipLaunchKernelGGL(owgs_health_padmin_kernel, dim3(1), dim3(1024), 0, st, reg_first, pad_src, new_size);
     hipLaunchKernelGGL(owgs_health_fsm_kernel, GRID(new_size), A);

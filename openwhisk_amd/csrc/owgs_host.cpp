@@ -102,7 +102,11 @@ extern "C" hipError_t owgs_launch_health_batch(const int32_t* ev_inv, const uint
                                                int32_t* idx_out, int64_t* packed, int32_t* seg_beg, int32_t* seg_end,
                                                int32_t* reg_first, int32_t* pad_src, uint8_t* s, uint32_t* ring,
                                                int64_t* last, int64_t* tick, int64_t* mem, int32_t* tests,
-                                               int32_t old_size, int32_t new_size, int64_t now, hipStream_t st);
+                                               int32_t old_size, int32_t new_size, int64_t now, int32_t* sum,
+                                               hipStream_t st);
+extern "C" hipError_t owgs_launch_ping_parse(const uint8_t* bytes, const int64_t* off, int32_t n, uint8_t* out_kind,
+                                             int32_t* out_inst, long long* out_mem, hipStream_t st);
+extern "C" hipError_t owgs_launch_feed_compact(const OwgsFeedArgs* a, int mode, hipStream_t st);
 extern "C" size_t owgs_msg_scratch_bytes(int32_t n, int32_t n_topics, int32_t bits);
 extern "C" hipError_t owgs_launch_msg_plan(const OwgsMsgArgs* a, int32_t bits, void* temp, size_t temp_bytes,
                                            uint32_t* key_sorted, int32_t* iota, int64_t* len_sorted, int32_t* cnt,
@@ -357,6 +361,12 @@ struct owgs_ctx {
     DevBuf<int64_t> h_last, h_tick, h_mem, he_t, he_mem, he_packed;
     DevBuf<int32_t> h_tests, he_inv, he_key, he_idx0, he_idx1, he_beg, he_end, he_reg, he_pad;
     int32_t h_cap = 0, h_size = 0;
+    // the supervision feeds (owgs_feeds.hip): the FSM kernel's summary words, the pings' receive times and parsed
+    // userMemory, and the largest batch whose feed buffers are reserved (feed_n) with its sort scratch (feed_tb)
+    DevBuf<int32_t> he_sum;
+    DevBuf<int64_t> pg_t, pg_mem;
+    int32_t feed_n = 0;
+    size_t feed_tb = 0;
     hipEvent_t ev_engine[2] = {nullptr, nullptr};  // around the last owgs_engine_kernel launch
     DevBuf<unsigned long long> r_bound;  // release front end scratch (owgs_launch_release_seq)
     DevBuf<int32_t> r_idx, r_cnt, r_cval, r_cval_s, r_cbeg;
@@ -1969,10 +1979,11 @@ void owgs_destroy(owgs_ctx* c) {
     c->he_kind.release();
     c->he_temp.release();
     c->h_ring.release();
-    DevBuf<int64_t>* h64[] = {&c->h_last, &c->h_tick, &c->h_mem, &c->he_t, &c->he_mem, &c->he_packed};
+    DevBuf<int64_t>* h64[] = {&c->h_last, &c->h_tick, &c->h_mem,  &c->he_t,
+                              &c->he_mem, &c->he_packed, &c->pg_t, &c->pg_mem};
     for (auto* b : h64) b->release();
     DevBuf<int32_t>* h32[] = {&c->h_tests, &c->he_inv, &c->he_key, &c->he_idx0, &c->he_idx1,
-                              &c->he_beg,  &c->he_end, &c->he_reg, &c->he_pad};
+                              &c->he_beg,  &c->he_end, &c->he_reg, &c->he_pad,  &c->he_sum};
     for (auto* b : h32) b->release();
     if (c->ev_engine[0]) (void)hipEventDestroy(c->ev_engine[0]);
     if (c->ev_engine[1]) (void)hipEventDestroy(c->ev_engine[1]);
@@ -4407,6 +4418,90 @@ static hipError_t grow_keep(DevBuf<T>& d, size_t cap, size_t keep, hipStream_t s
     return hipSuccess;
 }
 
+static int health_apply(owgs_ctx* c);
+
+// room for a status vector of new_size entries (a no-op when it is there)
+static int health_grow(owgs_ctx* c, int32_t new_size) {
+    hipStream_t st = c->stream;
+    if (new_size > c->h_cap) {
+        int32_t cap = c->h_cap ? c->h_cap : 1024;
+        while (cap < new_size) cap *= 2;
+        const size_t keep = (size_t)c->h_cap;
+        HIPCHK(c, grow_keep(c->h_st, cap, keep, st));
+        HIPCHK(c, grow_keep(c->h_ring, cap, keep, st));
+        HIPCHK(c, grow_keep(c->h_last, cap, keep, st));
+        HIPCHK(c, grow_keep(c->h_tick, cap, keep, st));
+        HIPCHK(c, grow_keep(c->h_mem, cap, keep, st));
+        HIPCHK(c, grow_keep(c->h_tests, cap, keep, st));
+        HIPCHK(c, owgs_launch_health_init(c->h_st.p, c->h_ring.p, c->h_last.p, c->h_tick.p, c->h_mem.p, c->h_tests.p,
+                                          c->h_cap, cap, st));
+        c->h_cap = cap;
+    }
+    return OWGS_OK;
+}
+
+// The batch itself, events in device arrays (the caller validated them and entered the context): owgs_health_events
+// after its uploads, and the supervision feeds, whose events owgs_feed_compact_kernel wrote.  max_id / max_ping = the
+// largest invoker of any event / of a ping (-1: none).  summary (may be null): [1] status entries changed, [2] test
+// actions sent.  apply: 0 hands nothing over, 1 hands the vector to updateInvokers, 2 only when an entry changed; 2 is
+// the feeds' mode and needs summary -- without one, any non-zero apply hands over, as owgs_health_events documents.
+static int health_batch(owgs_ctx* c, const int32_t* d_inv, const uint8_t* d_kind, const int64_t* d_t,
+                        const int64_t* d_mem, int32_t n, int32_t max_id, int32_t max_ping, int64_t now_ms,
+                        int32_t apply, int32_t* summary) {
+    hipStream_t st = c->stream;
+    const int32_t old_size = c->h_size;
+    const int32_t new_size = std::max(old_size, max_ping + 1);
+    {
+        const int rg = health_grow(c, new_size);
+        if (rg) return rg;
+    }
+    int32_t bits = 1;
+    while (bits < 31 && (max_id >> bits) != 0) ++bits;
+    const size_t tb = n ? owgs_health_sort_bytes(n, bits) : 0;
+    HIPCHK(c, c->he_temp.reserve(tb));
+    HIPCHK(c, c->he_key.reserve((size_t)n));
+    HIPCHK(c, c->he_idx0.reserve((size_t)n));
+    HIPCHK(c, c->he_idx1.reserve((size_t)n));
+    HIPCHK(c, c->he_packed.reserve((size_t)n));
+    HIPCHK(c, c->he_beg.reserve((size_t)new_size));
+    HIPCHK(c, c->he_end.reserve((size_t)new_size));
+    HIPCHK(c, c->he_reg.reserve((size_t)new_size));
+    HIPCHK(c, c->he_pad.reserve((size_t)new_size));
+    int32_t sum[2] = {0, 0};
+    if (summary) {
+        HIPCHK(c, c->he_sum.reserve(2));
+        HIPCHK(c, hipMemsetAsync(c->he_sum.p, 0, sizeof(sum), st));
+    }
+    HIPCHK(c, owgs_launch_health_batch(d_inv, d_kind, d_t, d_mem, n, bits, c->he_temp.p, tb,
+                                       c->he_key.p, c->he_idx0.p, c->he_idx1.p, c->he_packed.p, c->he_beg.p,
+                                       c->he_end.p, c->he_reg.p,
+                                       c->he_pad.p, c->h_st.p, c->h_ring.p, c->h_last.p, c->h_tick.p, c->h_mem.p,
+                                       c->h_tests.p, old_size, new_size, now_ms, summary ? c->he_sum.p : nullptr, st));
+    if (summary) HIPCHK(c, hipMemcpyAsync(sum, c->he_sum.p, sizeof(sum), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->h_size = new_size;
+    c->h_now = now_ms;
+    if (summary) {
+        summary[1] = sum[0];
+        summary[2] = sum[1];
+    }
+    if (!apply || (summary && apply == 2 && sum[0] == 0)) return OWGS_OK;
+    return health_apply(c);
+}
+
+static int health_apply(owgs_ctx* c) {
+    const int32_t new_size = c->h_size;
+    // CurrentInvokerPoolState -> monitor -> updateInvokers (SCPB:226-227): ids are the positions (InvokerPool keeps
+    // status(i).id.toInt == i, ISUP:186-191)
+    std::vector<int32_t> ids(new_size);
+    std::vector<int64_t> mem(new_size);
+    std::vector<uint8_t> sts(new_size);
+    int rc = owgs_health_read(c, new_size, nullptr, sts.data(), mem.data(), nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    for (int32_t i = 0; i < new_size; ++i) ids[i] = i;
+    return owgs_update_invokers(c, new_size, ids.data(), mem.data(), sts.data());
+}
+
 int owgs_health_events(owgs_ctx* c, int32_t n, const int32_t* invoker, const uint8_t* kind, const int64_t* t_ms,
                        const int64_t* user_memory_bytes, int64_t now_ms, int32_t apply) {
     if (!c || n < 0 || (n > 0 && (!invoker || !kind || !t_ms || !user_memory_bytes))) return OWGS_EINVAL;
@@ -4430,56 +4525,16 @@ int owgs_health_events(owgs_ctx* c, int32_t n, const int32_t* invoker, const uin
         if (ro_) return ro_;
     }
     hipStream_t st = c->stream;
-    const int32_t old_size = c->h_size;
-    const int32_t new_size = std::max(old_size, max_ping + 1);
-    if (new_size > c->h_cap) {
-        int32_t cap = c->h_cap ? c->h_cap : 1024;
-        while (cap < new_size) cap *= 2;
-        const size_t keep = (size_t)c->h_cap;
-        HIPCHK(c, grow_keep(c->h_st, cap, keep, st));
-        HIPCHK(c, grow_keep(c->h_ring, cap, keep, st));
-        HIPCHK(c, grow_keep(c->h_last, cap, keep, st));
-        HIPCHK(c, grow_keep(c->h_tick, cap, keep, st));
-        HIPCHK(c, grow_keep(c->h_mem, cap, keep, st));
-        HIPCHK(c, grow_keep(c->h_tests, cap, keep, st));
-        HIPCHK(c, owgs_launch_health_init(c->h_st.p, c->h_ring.p, c->h_last.p, c->h_tick.p, c->h_mem.p, c->h_tests.p,
-                                          c->h_cap, cap, st));
-        c->h_cap = cap;
+    {  // the vector's room before the uploads, as ever (health_batch then finds it there)
+        const int rg = health_grow(c, std::max(c->h_size, max_ping + 1));
+        if (rg) return rg;
     }
     HIPCHK(c, upload(c->he_inv, invoker, (size_t)n, st));
     HIPCHK(c, upload(c->he_kind, kind, (size_t)n, st));
     HIPCHK(c, upload(c->he_t, t_ms, (size_t)n, st));
     HIPCHK(c, upload(c->he_mem, user_memory_bytes, (size_t)n, st));
-    int32_t bits = 1;
-    while (bits < 31 && (max_id >> bits) != 0) ++bits;
-    const size_t tb = n ? owgs_health_sort_bytes(n, bits) : 0;
-    HIPCHK(c, c->he_temp.reserve(tb));
-    HIPCHK(c, c->he_key.reserve((size_t)n));
-    HIPCHK(c, c->he_idx0.reserve((size_t)n));
-    HIPCHK(c, c->he_idx1.reserve((size_t)n));
-    HIPCHK(c, c->he_packed.reserve((size_t)n));
-    HIPCHK(c, c->he_beg.reserve((size_t)new_size));
-    HIPCHK(c, c->he_end.reserve((size_t)new_size));
-    HIPCHK(c, c->he_reg.reserve((size_t)new_size));
-    HIPCHK(c, c->he_pad.reserve((size_t)new_size));
-    HIPCHK(c, owgs_launch_health_batch(c->he_inv.p, c->he_kind.p, c->he_t.p, c->he_mem.p, n, bits, c->he_temp.p, tb,
-                                       c->he_key.p, c->he_idx0.p, c->he_idx1.p, c->he_packed.p, c->he_beg.p,
-                                       c->he_end.p, c->he_reg.p,
-                                       c->he_pad.p, c->h_st.p, c->h_ring.p, c->h_last.p, c->h_tick.p, c->h_mem.p,
-                                       c->h_tests.p, old_size, new_size, now_ms, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    c->h_size = new_size;
-    c->h_now = now_ms;
-    if (!apply) return OWGS_OK;
-    // CurrentInvokerPoolState -> monitor -> updateInvokers (SCPB:226-227): ids are the positions (InvokerPool keeps
-    // status(i).id.toInt == i, ISUP:186-191)
-    std::vector<int32_t> ids(new_size);
-    std::vector<int64_t> mem(new_size);
-    std::vector<uint8_t> sts(new_size);
-    int rc = owgs_health_read(c, new_size, nullptr, sts.data(), mem.data(), nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    for (int32_t i = 0; i < new_size; ++i) ids[i] = i;
-    return owgs_update_invokers(c, new_size, ids.data(), mem.data(), sts.data());
+    return health_batch(c, c->he_inv.p, c->he_kind.p, c->he_t.p, c->he_mem.p, n, max_id, max_ping, now_ms,
+                        apply ? 1 : 0, nullptr);
 }
 
 int owgs_health_read(owgs_ctx* c, int32_t cap, int32_t* n, uint8_t* status, int64_t* user_memory_bytes,
@@ -4510,6 +4565,183 @@ int owgs_health_read(owgs_ctx* c, int32_t cap, int32_t* n, uint8_t* status, int6
         for (int32_t i = 0; i < m; ++i)
             if (next_tick[i] == INT64_MAX) next_tick[i] = -1;
     return OWGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------ supervision feeds
+// owgs_feeds.hip: the events are compacted on the device from the outcome buffers of the ping parser / the completion
+// path and handed to health_batch; the host only counts them in the outcome arrays it copies back anyway.
+
+// every buffer a feed of up to n events into the current status vector needs, so that nothing after the completion
+// path's first state-changing kernel can fail for want of memory (the vector itself only grows on pings)
+static int feed_reserve(owgs_ctx* c, int32_t n) {
+    if (n > c->feed_n) {
+        size_t tb = 0;
+        for (int32_t bits = 1; bits <= 24; ++bits) tb = std::max(tb, owgs_health_sort_bytes(n, bits));
+        c->feed_tb = tb;
+        c->feed_n = n;
+    }
+    const size_t m = (size_t)n, sz = (size_t)c->h_size;
+    HIPCHK(c, c->he_inv.reserve(m));
+    HIPCHK(c, c->he_kind.reserve(m));
+    HIPCHK(c, c->he_t.reserve(m));
+    HIPCHK(c, c->he_mem.reserve(m));
+    HIPCHK(c, c->he_temp.reserve(c->feed_tb));
+    HIPCHK(c, c->he_key.reserve(m));
+    HIPCHK(c, c->he_idx0.reserve(m));
+    HIPCHK(c, c->he_idx1.reserve(m));
+    HIPCHK(c, c->he_packed.reserve(m));
+    HIPCHK(c, c->he_beg.reserve(sz));
+    HIPCHK(c, c->he_end.reserve(sz));
+    HIPCHK(c, c->he_reg.reserve(sz));
+    HIPCHK(c, c->he_pad.reserve(sz));
+    HIPCHK(c, c->he_sum.reserve(2));
+    return OWGS_OK;
+}
+
+static int feed_args_ok(owgs_ctx* c, int64_t now_ms, int32_t apply) {
+    if (apply < 0 || apply > 2) return c->fail(OWGS_EINVAL, "feed: apply outside 0..2");
+    if (now_ms < 0 || now_ms >= (1LL << 60)) return c->fail(OWGS_EINVAL, "feed: now outside [0, 2^60)");
+    if (now_ms < c->h_now) return c->fail(OWGS_EINVAL, "feed: now before the health supervision's last batch");
+    return OWGS_OK;
+}
+
+// the completion outcomes of n items (device: kind / inv / flags / info as the completion path left them; host: the
+// copies the caller returns) -> InvocationFinishedMessage events at now_ms -> the FSM
+static int feed_acks(owgs_ctx* c, int32_t n, const uint8_t* h_kind, const int32_t* h_inv, const uint8_t* d_kind,
+                     const int32_t* d_inv, const uint8_t* d_flags, const uint8_t* d_info, int64_t now_ms,
+                     int32_t apply, int32_t out_summary[3]) {
+    int32_t cnt = 0, max_id = -1;
+    for (int32_t i = 0; i < n; ++i)
+        if ((h_kind[i] == OWGS_ACK_RELEASED || h_kind[i] == OWGS_ACK_HEALTH) && h_inv[i] >= 0 &&
+            h_inv[i] < OWGS_HEALTH_MAX_ID) {
+            ++cnt;
+            max_id = std::max(max_id, h_inv[i]);
+        }
+    out_summary[0] = cnt;
+    out_summary[1] = out_summary[2] = 0;
+    if (cnt == 0) {  // nothing for the pool: its clock stays (as after a sweep that expires nothing)
+        return apply == 1 && c->h_size > 0 ? health_apply(c) : OWGS_OK;
+    }
+    hipStream_t st = c->stream;
+    OwgsFeedArgs a{};
+    a.n = n;
+    a.kind = d_kind;
+    a.inv = d_inv;
+    a.flags = d_flags;
+    a.info = d_info;
+    a.now = now_ms;
+    a.ev_inv = c->he_inv.p;
+    a.ev_kind = c->he_kind.p;
+    a.ev_t = c->he_t.p;
+    a.ev_mem = c->he_mem.p;
+    HIPCHK(c, owgs_launch_feed_compact(&a, OWGS_FEED_ACKS, st));
+    return health_batch(c, c->he_inv.p, c->he_kind.p, c->he_t.p, c->he_mem.p, cnt, max_id, -1, now_ms, apply,
+                        out_summary);
+}
+
+int owgs_process_acks_supervised(owgs_ctx* c, int32_t n, const char* bytes, const int64_t* off, uint8_t* out_kind,
+                                 int32_t* out_invoker, int32_t* out_ticket, uint8_t* out_flags, int64_t now_ms,
+                                 int32_t apply, int32_t out_summary[3]) {
+    if (!c || n < 0 || !out_summary ||
+        (n > 0 && (!bytes || !off || !out_kind || !out_invoker || !out_ticket || !out_flags)))
+        return OWGS_EINVAL;
+    int rc = feed_args_ok(c, now_ms, apply);
+    if (rc) return rc;
+    OWGS_ENTER(c);
+    rc = feed_reserve(c, n);
+    if (rc) return rc;
+    rc = owgs_process_acks(c, n, bytes, off, out_kind, out_invoker, out_ticket, out_flags);
+    if (rc) return rc;
+    return feed_acks(c, n, out_kind, out_invoker, c->k_kind.p, c->k_act.p, c->k_oflags.p, c->k_info.p, now_ms, apply,
+                     out_summary);
+}
+
+int owgs_complete_activations_supervised(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* invoker,
+                                         const uint8_t* flags, uint8_t* out_kind, int32_t* out_ticket,
+                                         uint8_t* out_flags, int64_t now_ms, int32_t apply, int32_t out_summary[3]) {
+    if (!c || n < 0 || !out_summary || (n > 0 && (!aid32 || !invoker || !flags || !out_kind || !out_ticket || !out_flags)))
+        return OWGS_EINVAL;
+    int rc = feed_args_ok(c, now_ms, apply);
+    if (rc) return rc;
+    OWGS_ENTER(c);
+    rc = feed_reserve(c, n);
+    if (rc) return rc;
+    rc = owgs_complete_activations(c, n, aid32, invoker, flags, out_kind, out_ticket, out_flags);
+    if (rc) return rc;
+    return feed_acks(c, n, out_kind, invoker, c->k_kind.p, c->k_inst.p, c->k_oflags.p, c->k_info.p, now_ms, apply,
+                     out_summary);
+}
+
+int owgs_process_pings(owgs_ctx* c, int32_t n, const char* bytes, const int64_t* off, const int64_t* t_ms,
+                       int64_t now_ms, int32_t apply, uint8_t* out_kind, int32_t* out_instance,
+                       int64_t* out_user_memory_bytes, int32_t out_summary[3]) {
+    if (!c || n < 0 || !out_summary ||
+        (n > 0 && (!bytes || !off || !t_ms || !out_kind || !out_instance || !out_user_memory_bytes)))
+        return OWGS_EINVAL;
+    if (apply < 0 || apply > 2) return c->fail(OWGS_EINVAL, "pings: apply outside 0..2");
+    // the time contract of owgs_health_events over all n messages, whatever they parse to, before anything runs
+    int64_t prev = std::max(c->h_now, (int64_t)0);
+    for (int32_t i = 0; i < n; ++i) {
+        if (t_ms[i] < prev || t_ms[i] >= (1LL << 60))
+            return c->fail(OWGS_EINVAL, "pings: time before the previous one or outside [0, 2^60)");
+        prev = t_ms[i];
+        if (off[i + 1] < off[i] || off[i] < 0) return c->fail(OWGS_EINVAL, "offsets");
+    }
+    if (now_ms < prev || now_ms >= (1LL << 60))
+        return c->fail(OWGS_EINVAL, "pings: now before the last message or outside [0, 2^60)");
+    OWGS_ENTER(c);
+    {
+        const int ro_ = order_on(c, c->stream);
+        if (ro_) return ro_;
+    }
+    hipStream_t st = c->stream;
+    int32_t cnt = 0, max_id = -1;
+    if (n > 0) {
+        const size_t nb = (size_t)(off[n] - off[0]);
+        std::vector<int64_t> o((size_t)n + 1);
+        for (int32_t i = 0; i <= n; ++i) o[i] = off[i] - off[0];
+        HIPCHK(c, c->k_bytes.reserve(nb + 32));
+        HIPCHK(c, hipMemsetAsync(c->k_bytes.p + nb, 0, 32, st));
+        if (nb) HIPCHK(c, hipMemcpyAsync(c->k_bytes.p, bytes + off[0], nb, hipMemcpyHostToDevice, st));
+        HIPCHK(c, upload(c->k_off, o.data(), o.size(), st));
+        HIPCHK(c, upload(c->pg_t, t_ms, (size_t)n, st));
+        HIPCHK(c, c->k_kind.reserve((size_t)n));
+        HIPCHK(c, c->k_act.reserve((size_t)n));
+        HIPCHK(c, c->pg_mem.reserve((size_t)n));
+        HIPCHK(c, owgs_launch_ping_parse(c->k_bytes.p, c->k_off.p, n, c->k_kind.p, c->k_act.p,
+                                         (long long*)c->pg_mem.p, st));
+        HIPCHK(c, hipMemcpyAsync(out_kind, c->k_kind.p, (size_t)n, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out_instance, c->k_act.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out_user_memory_bytes, c->pg_mem.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        for (int32_t i = 0; i < n; ++i)
+            if (out_kind[i] == OWGS_PING_FED) {
+                ++cnt;
+                max_id = std::max(max_id, out_instance[i]);
+            }
+    }
+    out_summary[0] = cnt;
+    out_summary[1] = out_summary[2] = 0;
+    if (cnt > 0) {
+        HIPCHK(c, c->he_inv.reserve((size_t)cnt));
+        HIPCHK(c, c->he_kind.reserve((size_t)cnt));
+        HIPCHK(c, c->he_t.reserve((size_t)cnt));
+        HIPCHK(c, c->he_mem.reserve((size_t)cnt));
+        OwgsFeedArgs a{};
+        a.n = n;
+        a.kind = c->k_kind.p;
+        a.inv = c->k_act.p;
+        a.t = c->pg_t.p;
+        a.mem = c->pg_mem.p;
+        a.ev_inv = c->he_inv.p;
+        a.ev_kind = c->he_kind.p;
+        a.ev_t = c->he_t.p;
+        a.ev_mem = c->he_mem.p;
+        HIPCHK(c, owgs_launch_feed_compact(&a, OWGS_FEED_PINGS, st));
+    }
+    // every event is a ping: the vector grows to the largest instance; timers due up to now_ms fire either way
+    return health_batch(c, c->he_inv.p, c->he_kind.p, c->he_t.p, c->he_mem.p, cnt, max_id, max_id, now_ms, apply,
+                        out_summary);
 }
 
 // ------------------------------------------------------------------------------------------ ActivationMessage output

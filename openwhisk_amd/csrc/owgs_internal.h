@@ -546,6 +546,33 @@ struct OwgsLookupArgs {
 #define OWGS_ACK_FORCED_NOENTRY 6
 #endif
 #define OWGS_ACK_COMPLETION 3       // parsed CompletionMessage (before resolution into RELEASED / HEALTH / NOENTRY)
+// ping outcomes of owgs_ping_parse_kernel (= OWGS_PING_* in include/owgs.h)
+#ifndef OWGS_PING_FAIL
+#define OWGS_PING_FAIL 0
+#define OWGS_PING_UNSUPPORTED 2
+#define OWGS_PING_FED 3
+#define OWGS_PING_RANGE 4
+#endif
+#define OWGS_HEALTH_MAX_ID_V (1 << 24)  // OWGS_HEALTH_MAX_ID: ids the health status vector accepts
+
+// supervision feeds (owgs_feeds.hip): which outcome arrays the compaction reads
+#define OWGS_FEED_PINGS 0           // kind = OWGS_PING_*, inv = instance, t / mem per message
+#define OWGS_FEED_ACKS 1            // kind = OWGS_ACK_* outcomes, inv = the message's invoker, flags bit0 isSystemError,
+                                    // info bit6 forced; every event at time now with userMemory 0
+struct OwgsFeedArgs {
+    int32_t n;
+    const uint8_t* kind;         // [n] outcome of each item
+    const int32_t* inv;          // [n] its invoker
+    const uint8_t* flags;        // acks: [n] out_flags of the completion path
+    const uint8_t* info;         // acks: [n] the parse record (forced bit), null: nothing forced
+    const int64_t* t;            // pings: [n] receive time
+    const int64_t* mem;          // pings: [n] userMemory in bytes
+    long long now;               // acks: the time of every event
+    int32_t* ev_inv;             // out, [count] in item order
+    uint8_t* ev_kind;
+    int64_t* ev_t;
+    int64_t* ev_mem;
+};
 
 struct OwgsAckParseArgs {
     const uint8_t* bytes;        // messages, padded by >= 16 readable bytes

@@ -22,6 +22,7 @@ Configs (BASELINE.json "configs"):
 """
 from __future__ import annotations
 
+import json
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -202,6 +203,18 @@ def completion_message(aid: str, instance: int, system_error: bool = False, tid=
         instance, (',"uniqueName":"%s"' % unique_name) if unique_name else "", user_memory_mb)
     return ('{"transid":["%s",%d],"activationId":"%s","isSystemError":%s,"invoker":%s}' % (
         tid[0], tid[1], aid, "true" if system_error else "false", inv)).encode("ascii")
+
+
+def ping_message(instance: int, user_memory: str, unique: str | None = None, displayed: str | None = None) -> bytes:
+    """PingMessage(InvokerInstanceId(...)).serialize (Message.scala:257-259): jsonFormat(_, "name") compactPrint of
+    jsonFormat4's members in declaration order instance, uniqueName, displayedName, userMemory, None options omitted
+    (InstanceId.scala:31-49).  user_memory = ByteSize.toString, e.g. "16384 MB"."""
+    def js(x: str) -> str:
+        return json.dumps(x, ensure_ascii=False)
+    inv = '{"instance":%d%s%s,"userMemory":%s}' % (
+        instance, (',"uniqueName":' + js(unique)) if unique is not None else "",
+        (',"displayedName":' + js(displayed)) if displayed is not None else "", js(user_memory))
+    return ('{"name":%s}' % inv).encode("utf-8")
 
 
 def combined_message(aid: str, instance: int, user_memory_mb: int = 16384) -> bytes:
