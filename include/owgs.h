@@ -567,6 +567,81 @@ int owgs_serialize_activations_device(owgs_ctx* ctx, const owgs_msg_batch* batch
                                       int64_t cap, int64_t* out_off, int32_t* out_order, int32_t* topic_start,
                                       int64_t* total, int32_t* m, void* stream);
 
+/* ---- publish end to end: schedule, setupActivation, serialise ----
+ * Replaces: ShardingContainerPoolBalancer.publish (SCPB:257-317) for a drained batch -- schedule (SCPB:260-290), then
+ * for the activations that got an invoker setupActivation (SCPB:292-304, CLB:116-166) and sendActivationToInvoker
+ * (SCPB:302-303, CLB:175-198) -- as one call.  The decisions stay on the device from the engine through the
+ * activationSlots table into the serialiser; they come back once, with every other output.
+ *
+ * Sequential definition.  Item i, in array order:
+ *   1. Decision (SCPB:260-290): exactly owgs_publish_batch's for the same action, seq and seq_base.  out_invoker[i]
+ *      >= 0, OWGS_NONE or OWGS_THROW_INDEX; out_flags[i] bit 0 the overload flag.
+ *   2. Only if out_invoker[i] >= 0 (SCPB:292-304): setupActivation (CLB:116-166), exactly owgs_track_activations_timed
+ *      for the item with invoker = out_invoker[i] and now_ms = io->now_ms.  The books count the item whether or not its
+ *      id already has an entry (CLB:121-127 run before getOrElseUpdate, CLB:148).  The item that creates the entry
+ *      stores namespace, action, ticket and invoker and arms now + max(time_limit, std) * factor + addon (CLB:103-105,
+ *      148-152).  A duplicate of an earlier PLACED item of the batch, or of an existing entry, gets that entry's ticket,
+ *      out_existed = 1, and arms nothing.  An item without an invoker touches neither the table nor any counter and
+ *      cannot be the first tracker of an id (SCPB:305-316 never reach setupActivation): out_ticket = -1, out_existed =
+ *      0.  Arm order among the placed items is array order; the context's arm counter advances by n.
+ *   3. With msgs: the item's message is written under topic "invoker<out_invoker[i]>" exactly as
+ *      owgs_serialize_activations would with invoker = out_invoker; an item without an invoker gets no message.
+ * Step 1 never reads what steps 2 and 3 write, so running the stages batch-wise equals running them item by item.
+ * Only placed jobs are counted: for callers of this entry point the "assumption" of owgs_throttle_batch /
+ * owgs_admit_batch (an admitted job is tracked afterwards) is no longer a hazard -- a job without an invoker is not
+ * counted against the later jobs of its namespace once this call has run.
+ *
+ * The ids are (hi, lo) words (owgs_msg_batch.aid; hi = the first 16 hex digits): the entry is the one a raw ack with
+ * the 32-hex id finds and the one owgs_expire_activations reports in out_aid.
+ *
+ * msgs and mo are both NULL (stages 1 and 2 only) or both set.  With them: msgs->n == io->n; msgs->invoker and
+ * msgs->aid must be NULL (the call uses its own decisions and io->aid); everything else as owgs_serialize_activations.
+ *
+ * out_summary: [0] placed items, [1] entries created, [2] overload fallbacks of managed actions
+ * (MANAGED_SYSTEM_OVERLOAD, SCPB:277-286), [3] of blackbox actions (BLACKBOX_SYSTEM_OVERLOAD), [4] items with
+ * OWGS_NONE, [5] items with OWGS_THROW_INDEX, [6] stages completed (0, 2 or 3), [7] 0.
+ *
+ * Failures.  Argument errors are refused before any state changes, the slot state included, with the code of the
+ * corresponding call: a NULL among the required pointers (every io pointer but seq and ns; out_summary), n < 0, msgs
+ * without mo or mo without msgs, msgs->n != io->n, msgs->invoker or msgs->aid set, now_ms outside [0, 2^60), a time
+ * limit outside [0, 2^40) and every host-side check of owgs_serialize_activations: OWGS_EINVAL; an unknown action or
+ * namespace handle: OWGS_ENOENT.  n == 0 is OWGS_OK and changes nothing.  An engine error (the codes of
+ * owgs_publish_batch) means nothing is tracked and nothing is written.  A failure the message stage finds on the device
+ * -- an unknown template, an invoker >= n_topics, a transaction id that is not valid UTF-8 (OWGS_EINVAL), total > cap
+ * (OWGS_ERANGE, mo->total set) -- does not undo stages 1 and 2, as the reference's setupActivation precedes a
+ * producer.send that may fail (SCPB:302-303; the entry is left to its timeout): the four io outputs and out_summary
+ * are valid, out_summary[6] = 2, and the caller serialises again with owgs_serialize_activations(invoker = out_invoker).
+ */
+typedef struct owgs_publish_io {
+    int32_t n;
+    const int32_t* action;         /* [n] action handles (owgs_register_actions) */
+    const uint64_t* seq;           /* [n] overload-RNG sequence numbers, or NULL: seq_base + i */
+    uint64_t seq_base;
+    const uint64_t* aid;           /* [2n] ActivationId as (hi, lo), the form of owgs_msg_batch.aid */
+    const int32_t* ns;             /* [n] namespace handles or OWGS_NONE; NULL: every item OWGS_NONE */
+    const int32_t* ticket;         /* [n] */
+    const int64_t* time_limit_ms;  /* [n] action.limits.timeout */
+    int64_t now_ms;
+    int32_t* out_invoker;          /* as owgs_publish_batch */
+    uint8_t* out_flags;            /* as owgs_publish_batch */
+    int32_t* out_ticket;           /* as owgs_track_activations_timed; -1 for an item without an invoker */
+    uint8_t* out_existed;          /* 0 / 1 as there; 0 for an item without an invoker */
+} owgs_publish_io;
+
+typedef struct owgs_msg_out {      /* the outputs of owgs_serialize_activations, host buffers */
+    int32_t n_topics;
+    char* out;
+    int64_t cap;
+    int64_t* out_off;
+    int32_t* out_order;
+    int32_t* topic_start;
+    int64_t total;                 /* written by the call */
+    int32_t m;
+} owgs_msg_out;
+
+int owgs_publish_activations(owgs_ctx* ctx, const owgs_publish_io* io, const owgs_msg_batch* msgs, owgs_msg_out* mo,
+                             int64_t out_summary[8]);
+
 /* Duration of the last owgs_engine_kernel launch (HIP events recorded on its stream right before and after it);
  * waits for it to finish.  Measurement hook for bench.py's roofline. */
 int owgs_engine_ms(owgs_ctx* ctx, float* ms);

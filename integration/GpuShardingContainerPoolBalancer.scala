@@ -55,6 +55,12 @@ object OwgsNative {
    *  sequence numbers are seqBase, seqBase + 1, ... in queue order. */
   @native def processBatch(ctx: Long, in: ByteBuffer, out: ByteBuffer, nRuns: Int, nRel: Int, nPub: Int,
                            seqBase: Long): Int
+  /** owgs_publish_activations (two-stage form) over direct buffers (native byte order), layout in PublishBuffers:
+   *  schedule, then setupActivation on the device for every activation that got an invoker (SCPB:257-304), its
+   *  completion-ack timer armed at nowMs.  For a shim that keeps activationSlots on the device (INTEGRATION.md §2);
+   *  the batcher below keeps calling processBatch. */
+  @native def publishActivations(ctx: Long, in: ByteBuffer, out: ByteBuffer, n: Int, hasNs: Boolean, seqBase: Long,
+                                 nowMs: Long): Int
   /** owgs_release_actions: handles of cold fqn@version keys (none of their activations in flight) */
   @native def releaseActions(ctx: Long, handles: Array[Int], n: Int): Int
   /** owgs_track_activations_timed: setupActivation's getOrElseUpdate with the entry's invoker and time limit, so that
@@ -89,6 +95,18 @@ object OwgsNative {
                                             outFlags: Array[Byte], nowMs: Long, apply: Int,
                                             outSummary: Array[Int]): Int
   @native def lastError(ctx: Long): String
+}
+
+/** The direct buffers of one publishActivations call (owgs_jni.c reads the same layout):
+ *  in  = aid[2 n] (hi, lo longs), timeLimitMs[n] (longs), action[n], ns[n], ticket[n] (ints);
+ *  out = summary[8] (longs), outInvoker[n], outTicket[n] (ints), outFlags[n], outExisted[n] (bytes). */
+final class PublishBuffers {
+  var in: ByteBuffer = ByteBuffer.allocateDirect(1 << 16).order(ByteOrder.nativeOrder())
+  var out: ByteBuffer = ByteBuffer.allocateDirect(1 << 15).order(ByteOrder.nativeOrder())
+  def ensure(n: Int): Unit = {
+    if (in.capacity < 36 * n) in = ByteBuffer.allocateDirect(72 * n).order(ByteOrder.nativeOrder())
+    if (out.capacity < 64 + 10 * n) out = ByteBuffer.allocateDirect(128 + 20 * n).order(ByteOrder.nativeOrder())
+  }
 }
 
 /** The direct buffers of one drained batch (owgs_jni.c processBatch reads the same layout):

@@ -130,6 +130,39 @@ JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00
                               pub_act, NULL, (uint64_t)seq_base, (int32_t*)po, (uint8_t*)(po + 4 * (jlong)n_pub));
 }
 
+/* publish end to end for one drained batch (owgs_publish_activations, two-stage form: msgs = NULL) over direct
+ * buffers, layout as PublishBuffers in the Scala shim:
+ * in  = aid[2 n] (hi, lo), time_limit_ms[n] (int64), action[n], ns[n], ticket[n] (int32); ns is read only with has_ns;
+ * out = summary[8] (int64), out_invoker[n], out_ticket[n] (int32), out_flags[n], out_existed[n] (bytes).
+ * Sequence numbers as processBatch. */
+JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_publishActivations(
+    JNIEnv* env, jobject self, jlong h, jobject in, jobject out, jint n, jboolean has_ns, jlong seq_base,
+    jlong now_ms) {
+    if (!in || !out || n < 0) return OWGS_EINVAL;
+    char* pi = (char*)(*env)->GetDirectBufferAddress(env, in);
+    char* po = (char*)(*env)->GetDirectBufferAddress(env, out);
+    if (!pi || !po) return OWGS_EINVAL;  /* not direct buffers */
+    if ((*env)->GetDirectBufferCapacity(env, in) < 36 * (jlong)n ||
+        (*env)->GetDirectBufferCapacity(env, out) < 64 + 10 * (jlong)n)
+        return OWGS_EINVAL;
+    owgs_publish_io io;
+    memset(&io, 0, sizeof io);
+    io.n = n;
+    io.aid = (const uint64_t*)pi;
+    io.time_limit_ms = (const int64_t*)(pi + 16 * (jlong)n);
+    io.action = (const int32_t*)(pi + 24 * (jlong)n);
+    io.ns = has_ns ? io.action + n : NULL;
+    io.ticket = io.action + 2 * (jlong)n;
+    io.seq = NULL;
+    io.seq_base = (uint64_t)seq_base;
+    io.now_ms = now_ms;
+    io.out_invoker = (int32_t*)(po + 64);
+    io.out_ticket = io.out_invoker + n;
+    io.out_flags = (uint8_t*)(po + 64 + 8 * (jlong)n);
+    io.out_existed = io.out_flags + n;
+    return owgs_publish_activations(CTX(h), &io, NULL, NULL, (int64_t*)po);
+}
+
 /* handles of cold fqn@version keys (owgs_release_actions) */
 JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_releaseActions(
     JNIEnv* env, jobject self, jlong h, jintArray handles, jint n) {

@@ -63,6 +63,20 @@ class owgs_msg_batch(C.Structure):
         "trace_off")]
 
 
+class owgs_publish_io(C.Structure):
+    """include/owgs.h: owgs_publish_io (the inputs and the four outputs of owgs_publish_activations)."""
+    _fields_ = [("n", C.c_int32), ("action", C.c_void_p), ("seq", C.c_void_p), ("seq_base", C.c_uint64),
+                ("aid", C.c_void_p), ("ns", C.c_void_p), ("ticket", C.c_void_p), ("time_limit_ms", C.c_void_p),
+                ("now_ms", C.c_int64), ("out_invoker", C.c_void_p), ("out_flags", C.c_void_p),
+                ("out_ticket", C.c_void_p), ("out_existed", C.c_void_p)]
+
+
+class owgs_msg_out(C.Structure):
+    """include/owgs.h: owgs_msg_out (the outputs of owgs_serialize_activations as host buffers)."""
+    _fields_ = [("n_topics", C.c_int32), ("out", C.c_void_p), ("cap", C.c_int64), ("out_off", C.c_void_p),
+                ("out_order", C.c_void_p), ("topic_start", C.c_void_p), ("total", C.c_int64), ("m", C.c_int32)]
+
+
 def build(verbose: bool = False) -> str:
     """Compile libowgs.so for gfx950 in-tree."""
     out = subprocess.run(["make", "-s", "-C", PKG], capture_output=not verbose, text=True)
@@ -110,6 +124,7 @@ def lib() -> C.CDLL:
         "owgs_set_root_controller": (C.c_int, [P, C.c_char_p, i32]),
         "owgs_serialize_activations": (C.c_int, [P, P, i32, P, C.c_int64, P, P, P, P, P]),
         "owgs_serialize_activations_device": (C.c_int, [P, P, i32, P, C.c_int64, P, P, P, P, P, P]),
+        "owgs_publish_activations": (C.c_int, [P, P, P, P, P]),
         "owgs_health_read": (C.c_int, [P, i32, P, P, P, P, P, P]),
         "owgs_process_pings": (C.c_int, [P, i32, P, P, P, C.c_int64, i32, P, P, P, P]),
         "owgs_process_acks_supervised": (C.c_int, [P, i32, P, P, P, P, P, P, C.c_int64, i32, P]),

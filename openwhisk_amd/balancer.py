@@ -616,6 +616,82 @@ class GpuShardingContainerPoolBalancer:
                                              _p(fl)))
         return out[:n], fl[:n]
 
+    def publish_activations(self, actions, aids, tickets, time_limit_ms, now_ms: int, ns=None, seq=None,
+                            seq_base: int = 0, msgs: dict | None = None):
+        """publish (SCPB:257-317) for a drained batch in one call (owgs_publish_activations): the decision of
+        `publish`, then for every activation that got an invoker setupActivation as `track_activations_timed` with that
+        invoker, and -- with `msgs` -- the serialised messages as `serialize_activations` with those decisions.
+        aids: 32-hex-digit strings.  msgs: the keyword arguments of serialize_activations without invoker and aid_words
+        (tmpl, tids, tid_start, flags, contents, causes, traces, n_topics, cap; n_topics and cap are required).
+        Returns (invoker, flags, ticket, existed, summary), plus (bytes, out_off, out_order, topic_start) with msgs.
+        A failure the message stage finds raises OwgsError with `.partial` = the five values above (stages 1 and 2 are
+        done) and `.total` = the bytes needed."""
+        from ._lib import owgs_msg_batch, owgs_msg_out, owgs_publish_io
+        a = np.ascontiguousarray(actions, dtype=np.int32)
+        n = len(a)
+        tk = np.ascontiguousarray(tickets, dtype=np.int32)
+        tl = np.ascontiguousarray(time_limit_ms, dtype=np.int64)
+        if not (len(aids) == len(tk) == len(tl) == n):
+            raise ValueError("publish_activations: arrays of different lengths")
+        w = np.zeros(max(2 * n, 2), dtype=np.uint64)
+        vals = [int(x, 16) for x in aids]
+        w[0:2 * n:2] = [v >> 64 for v in vals]
+        w[1:2 * n:2] = [v & (2**64 - 1) for v in vals]
+        h = None
+        if ns is not None:
+            h = np.ascontiguousarray(ns, dtype=np.int32)
+            if len(h) != n:
+                raise ValueError("ns needs one handle per activation")
+        sq = None if seq is None else np.ascontiguousarray(seq, dtype=np.uint64)
+        inv = np.zeros(max(n, 1), dtype=np.int32)
+        fl = np.zeros(max(n, 1), dtype=np.uint8)
+        ot = np.zeros(max(n, 1), dtype=np.int32)
+        ex = np.zeros(max(n, 1), dtype=np.uint8)
+        summ = np.zeros(8, dtype=np.int64)
+        z32, z64 = np.zeros(1, np.int32), np.zeros(1, np.int64)
+        io = owgs_publish_io(n, _p(a if n else z32), None if sq is None else _p(sq), int(seq_base), _p(w),
+                             None if h is None else _p(h if n else z32), _p(tk if n else z32), _p(tl if n else z64),
+                             int(now_ms), _p(inv), _p(fl), _p(ot), _p(ex))
+        if msgs is None:
+            self._chk(self._L.owgs_publish_activations(self._h, C.byref(io), None, None, _p(summ)))
+            return inv[:n], fl[:n], ot[:n], ex[:n], summ
+        tm = np.ascontiguousarray(msgs["tmpl"], dtype=np.int32)
+        tb, to = _blob(msgs["tids"])
+        ts = np.ascontiguousarray(msgs["tid_start"], dtype=np.int64)
+        mf = np.ascontiguousarray(msgs["flags"], dtype=np.uint8)
+        if not (len(tm) == len(ts) == len(mf) == len(to) - 1 == n):
+            raise ValueError("publish_activations: msgs arrays of different lengths")
+        keep = [tm, tb, to, ts, mf]
+        B = owgs_msg_batch(n, None, _p(tm), None, _p(tb), _p(to), _p(ts), _p(mf))
+        if msgs.get("contents") is not None:
+            cb, co = _blob(msgs["contents"])
+            keep += [cb, co]
+            B.content, B.content_off = _p(cb), _p(co)
+        if msgs.get("causes") is not None:
+            cz = np.ascontiguousarray(msgs["causes"], dtype=np.uint64).reshape(-1)
+            keep.append(cz)
+            B.cause = _p(cz)
+        if msgs.get("traces") is not None:
+            rb, ro = _blob(msgs["traces"])
+            keep += [rb, ro]
+            B.trace, B.trace_off = _p(rb), _p(ro)
+        nt, cap = int(msgs["n_topics"]), int(msgs["cap"])
+        off = np.zeros(n + 1, np.int64)
+        order = np.zeros(max(n, 1), np.int32)
+        topic = np.zeros(nt + 1, np.int32)
+        out = C.create_string_buffer(max(cap, 1))
+        mo = owgs_msg_out(nt, C.cast(out, C.c_void_p), cap, _p(off), _p(order), _p(topic), 0, 0)
+        rc = self._L.owgs_publish_activations(self._h, C.byref(io), C.byref(B), C.byref(mo), _p(summ))
+        del keep
+        if rc < 0:
+            e = OwgsError(rc, (self._L.owgs_last_error(self._h) or b"").decode())
+            if summ[6] == 2:
+                e.partial = (inv[:n], fl[:n], ot[:n], ex[:n], summ)
+                e.total = int(mo.total)
+            raise e
+        mm = mo.m
+        return inv[:n], fl[:n], ot[:n], ex[:n], summ, (out.raw[:mo.total], off[:mm + 1], order[:mm], topic)
+
     def release_invoker(self, invokers, actions) -> np.ndarray:
         """releaseInvoker (SCPB:327-331) per completion; returns release flags."""
         inv = np.ascontiguousarray(invokers, dtype=np.int32)

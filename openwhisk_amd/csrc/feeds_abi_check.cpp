@@ -39,6 +39,27 @@ int main() {
     EXPECT(owgs_complete_activations_supervised(nullptr, 1, aid, inv, cfl, kind, ticket, flags, int64_t(1) << 60, 2, summary),
            OWGS_EINVAL);
 
+    // owgs_publish_activations: no context, no io, no summary
+    const int32_t act[1] = {0};
+    const uint64_t words[2] = {1, 2};
+    const int64_t lim[1] = {100};
+    uint8_t existed[1];
+    int64_t psum[8];
+    owgs_publish_io io;
+    std::memset(&io, 0, sizeof io);
+    io.n = 1;
+    io.action = act;
+    io.aid = words;
+    io.ticket = inv;
+    io.time_limit_ms = lim;
+    io.out_invoker = inst;
+    io.out_flags = flags;
+    io.out_ticket = ticket;
+    io.out_existed = existed;
+    EXPECT(owgs_publish_activations(nullptr, &io, nullptr, nullptr, psum), OWGS_EINVAL);
+    EXPECT(owgs_publish_activations(nullptr, nullptr, nullptr, nullptr, psum), OWGS_EINVAL);
+    EXPECT(owgs_publish_activations(nullptr, &io, nullptr, nullptr, nullptr), OWGS_EINVAL);
+
     std::printf(g_bad ? "feeds_abi_check: %d failures\n" : "feeds_abi_check: ok\n", g_bad);
     return g_bad ? 1 : 0;
 }

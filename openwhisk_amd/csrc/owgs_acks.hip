@@ -610,11 +610,19 @@ __device__ __forceinline__ void mb_totals_add(unsigned long long* counters, int 
     }
 }
 
-// track step 1: find or claim a slot for every id of the batch
+// track step 1: find or claim a slot for every id of the batch.  placed (null: every item) is the predicate of
+// owgs_publish_activations: an item without an invoker skips setupActivation altogether (SCPB:292-304), so it claims
+// nothing, owns no slot and -- unlike state 3 below -- is not counted by the fill kernel (state 4).
 __global__ __launch_bounds__(256) void owgs_act_claim_kernel(OwgsActTable T, const ulonglong2* key, int32_t n,
-                                                             const uint8_t* info, int32_t* slot, uint8_t* state) {
+                                                             const uint8_t* info, const uint8_t* placed,
+                                                             int32_t* slot, uint8_t* state) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    if (placed && !placed[i]) {
+        slot[i] = -1;
+        state[i] = 4;
+        return;
+    }
     if (info && (info[i] & 7) != OWGS_ACK_COMPLETION) {
         slot[i] = -1;
         state[i] = 3;
@@ -664,13 +672,15 @@ __global__ __launch_bounds__(256) void owgs_act_claim_kernel(OwgsActTable T, con
 __global__ __launch_bounds__(256) void owgs_act_fill_kernel(OwgsActTable T, const ulonglong2* key, int32_t n,
                                                             const int32_t* action, const int32_t* ns,
                                                             const int32_t* ticket, const int32_t* slot,
-                                                            const uint8_t* state, int32_t* out_ticket,
-                                                            uint8_t* out_existed, unsigned long long* counters,
-                                                            OwgsInflight F, OwgsArm A) {
+                                                            const uint8_t* state, const uint8_t* placed,
+                                                            int32_t* out_ticket, uint8_t* out_existed,
+                                                            unsigned long long* counters, OwgsInflight F, OwgsArm A) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     int h = OWGS_NONE_V, mb = 0;
     bool bb = false;
-    if (i < n) {
+    // an item the gate did not place moves no counter and keeps the outputs the gate wrote; its lane still takes part
+    // in the wave / block reductions below with OWGS_NONE_V and 0 MB
+    if (i < n && (!placed || placed[i])) {
         const int a = action[i];
         h = ns ? ns[i] : OWGS_NONE_V;  // msg.user.namespace.uuid's handle (CLB:127)
         mb = F.act_mem[a];           // action.limits.memory.megabytes (CLB:125)
@@ -713,9 +723,9 @@ __global__ __launch_bounds__(256) void owgs_act_fill_kernel(OwgsActTable T, cons
 
 // track step 3: publish the claimed slots and reset the owner words
 __global__ __launch_bounds__(256) void owgs_act_publish_kernel(OwgsActTable T, int32_t n, const int32_t* slot,
-                                                               const uint8_t* state) {
+                                                               const uint8_t* state, const uint8_t* placed) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n || (placed && !placed[i])) return;
     const int s = slot[i];
     if (s < 0 || state[i] != 0 || T.owner[s] != i) return;
     T.tw[s] = TW_READY;
@@ -886,12 +896,12 @@ extern "C" hipError_t owgs_launch_act_track(const OwgsActTable* T, const ulonglo
                                             const int32_t* action, const int32_t* ns, const int32_t* ticket,
                                             int32_t* slot, uint8_t* state, int32_t* out_ticket, uint8_t* out_existed,
                                             unsigned long long* counters, const OwgsInflight* F, const OwgsArm* arm,
-                                            hipStream_t st) {
+                                            const uint8_t* placed, hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(owgs_act_claim_kernel, GRID(n), *T, key, n, (const uint8_t*)nullptr, slot, state);
-    hipLaunchKernelGGL(owgs_act_fill_kernel, GRID(n), *T, key, n, action, ns, ticket, slot, state, out_ticket,
+    hipLaunchKernelGGL(owgs_act_claim_kernel, GRID(n), *T, key, n, (const uint8_t*)nullptr, placed, slot, state);
+    hipLaunchKernelGGL(owgs_act_fill_kernel, GRID(n), *T, key, n, action, ns, ticket, slot, state, placed, out_ticket,
                        out_existed, counters, *F, *arm);
-    hipLaunchKernelGGL(owgs_act_publish_kernel, GRID(n), *T, n, slot, state);
+    hipLaunchKernelGGL(owgs_act_publish_kernel, GRID(n), *T, n, slot, state, placed);
     return hipGetLastError();
 }
 

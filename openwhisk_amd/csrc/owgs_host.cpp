@@ -67,7 +67,11 @@ extern "C" hipError_t owgs_launch_act_track(const OwgsActTable* T, const ulonglo
                                             const int32_t* action, const int32_t* ns, const int32_t* ticket,
                                             int32_t* slot, uint8_t* state, int32_t* out_ticket, uint8_t* out_existed,
                                             unsigned long long* counters, const OwgsInflight* F, const OwgsArm* arm,
-                                            hipStream_t st);
+                                            const uint8_t* placed, hipStream_t st);
+extern "C" hipError_t owgs_launch_publish_gate(const OwgsPublishGate* g, hipStream_t st);
+extern "C" hipError_t owgs_launch_publish_collect(unsigned long long* hdr, const int32_t* bad,
+                                                  const int32_t* topic_start, int32_t n_topics,
+                                                  const int64_t* out_off, int32_t n, hipStream_t st);
 extern "C" hipError_t owgs_launch_expire_scan(const OwgsExpireArgs* a, hipStream_t st);
 extern "C" size_t owgs_expire_sort_bytes(int32_t n);
 extern "C" hipError_t owgs_launch_expire_order(const OwgsExpireArgs* a, int32_t n, int32_t take, int32_t seq_bits,
@@ -355,6 +359,12 @@ struct owgs_ctx {
     DevBuf<int64_t> k_off;
     DevBuf<char> k_aid;
     DevBuf<unsigned long long> k_cnt;
+    // owgs_publish_activations (owgs_publish.hip): the placed predicate, the message stage's invoker array, the output
+    // block on the device and the pinned host block it is read back into with one copy
+    DevBuf<uint8_t> p_placed, p_blk;
+    DevBuf<int32_t> p_minv;
+    void* p_pin = nullptr;
+    size_t p_pin_bytes = 0;
     // invoker health supervision (owgs_health.hip): persistent SoA by invoker id + per-batch scratch
     DevBuf<uint8_t> h_st, he_kind, he_temp;
     DevBuf<uint32_t> h_ring;
@@ -1719,7 +1729,7 @@ static int seq_host_runs(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, co
     S.out_inv = c->d_out.p;
     S.out_flags = c->d_flags.p;
     const int rc = seq_run(c, S, s);
-    if (NP) {
+    if (NP && out_inv) {  // (null: the decisions stay in d_out / d_flags for owgs_publish_activations)
         HIPCHK(c, hipMemcpyAsync(out_inv, c->d_out.p, (size_t)NP * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(out_flags, c->d_flags.p, (size_t)NP, hipMemcpyDeviceToHost, s));
     }
@@ -1935,6 +1945,11 @@ void owgs_destroy(owgs_ctx* c) {
     c->k_off.release();
     c->k_aid.release();
     c->k_cnt.release();
+    c->p_placed.release();
+    c->p_blk.release();
+    c->p_minv.release();
+    if (c->p_pin) (void)hipHostFree(c->p_pin);
+    c->p_pin = nullptr;
     DevBuf<char>* mc[] = {&c->m_ta, &c->m_tb, &c->m_rci, &c->m_tid, &c->m_content, &c->m_trace, &c->m_out};
     for (auto* b : mc) b->release();
     DevBuf<int64_t>* m64[] = {&c->m_ta_off, &c->m_tb_off, &c->m_tid_off, &c->m_tid_start, &c->m_content_off,
@@ -2284,20 +2299,18 @@ int owgs_release_actions(owgs_ctx* c, int32_t n, const int32_t* actions) {
     return OWGS_OK;
 }
 
-int owgs_publish_batch(owgs_ctx* c, int32_t n, const int32_t* action, const uint64_t* seq, uint64_t seq_base,
-                       int32_t* out_invoker, uint8_t* out_flags) {
-    if (!c || n < 0 || (n > 0 && (!action || !out_invoker || !out_flags))) return OWGS_EINVAL;
-    const CallTimer timer_(c);
-    if (n == 0) return OWGS_OK;
-    if (!registered(c, n, action)) return c->fail(OWGS_ENOENT, "unknown action");
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
+}  // extern "C"
+
+// The device half of the scheduling step (SCPB:257-290) for n activations, shared by owgs_publish_batch and
+// owgs_publish_activations: the launch chain of an on-chip context (with the watched pairs' update), or the
+// large-state engine.  The decisions stay in c->d_out / c->d_flags and the action handles in c->d_a, queued on the
+// context's stream.  On a large-state context the engine's run synchronises and reports its own errors; h_out /
+// h_flags (nullable) then also receive the decisions as seq_host_runs copies them.
+static int publish_device(owgs_ctx* c, int32_t n, const int32_t* action, const uint64_t* seq, uint64_t seq_base,
+                          int32_t* h_out, uint8_t* h_flags) {
     if (c->large) {
         const int32_t ro[2] = {0, 0}, po[2] = {0, n};
-        return seq_host_runs(c, 1, ro, nullptr, nullptr, nullptr, po, action, seq, seq_base, out_invoker, out_flags);
+        return seq_host_runs(c, 1, ro, nullptr, nullptr, nullptr, po, action, seq, seq_base, h_out, h_flags);
     }
     const int64_t off[2] = {0, n};
     HIPCHK(c, upload(c->d_off, off, 2, c->stream));
@@ -2314,7 +2327,24 @@ int owgs_publish_batch(owgs_ctx* c, int32_t n, const int32_t* action, const uint
     int rc = run_prepass(c, A, 1, c->d_off.p, c->d_a.p, n, c->stream);
     if (!rc) rc = run_engine(c, A, c->stream);
     if (!rc) rc = w_update(c, n, c->d_a.p, c->d_out.p, c->d_flags.p, c->stream);
-    if (rc) return rc;
+    return rc;
+}
+
+extern "C" {
+
+int owgs_publish_batch(owgs_ctx* c, int32_t n, const int32_t* action, const uint64_t* seq, uint64_t seq_base,
+                       int32_t* out_invoker, uint8_t* out_flags) {
+    if (!c || n < 0 || (n > 0 && (!action || !out_invoker || !out_flags))) return OWGS_EINVAL;
+    const CallTimer timer_(c);
+    if (n == 0) return OWGS_OK;
+    if (!registered(c, n, action)) return c->fail(OWGS_ENOENT, "unknown action");
+    OWGS_ENTER(c);
+    {
+        const int ro_ = order_on(c, c->stream);
+        if (ro_) return ro_;
+    }
+    const int rc = publish_device(c, n, action, seq, seq_base, out_invoker, out_flags);
+    if (rc || c->large) return rc;  // (the large-state engine's run copied the decisions and waited)
     HIPCHK(c, hipMemcpyAsync(out_invoker, c->d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(out_flags, c->d_flags.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3736,6 +3766,35 @@ static OwgsInflight inflight_args(owgs_ctx* c) {
     return F;
 }
 
+// The device half of setupActivation (CLB:116-166) over device arrays: claim / fill / publish for n ids with their
+// action, namespace (null: none), ticket, entry invoker and time limit (inv null: an untimed call, nothing armed),
+// shared by the track entry points and owgs_publish_activations.  placed (null: every item) is the latter's predicate:
+// an item it clears touches neither the table nor a counter and keeps the out_ticket / out_existed already there.
+// The caller has run act_reserve(c, n) and zeroed counters; queued on st, no wait.  The arm counter advances by n.
+static int track_device(owgs_ctx* c, int32_t n, const ulonglong2* key, const int32_t* action, const int32_t* ns,
+                        const int32_t* ticket, const int32_t* inv, const long long* tl, int64_t now_ms,
+                        const uint8_t* placed, int32_t* out_ticket, uint8_t* out_existed,
+                        unsigned long long* counters, hipStream_t st) {
+    HIPCHK(c, c->k_slot.reserve((size_t)n));
+    HIPCHK(c, c->k_state.reserve((size_t)n));
+    OwgsArm arm{};
+    arm.seq_base = c->arm_seq;
+    if (inv) {
+        arm.inv = inv;
+        arm.tl = tl;
+        arm.now = now_ms;
+        arm.std_ms = c->a_std;
+        arm.factor = c->a_factor;
+        arm.addon = c->a_addon;
+    }
+    OwgsActTable T = act_table(c);
+    const OwgsInflight F = inflight_args(c);
+    HIPCHK(c, owgs_launch_act_track(&T, key, n, action, ns, ticket, c->k_slot.p, c->k_state.p, out_ticket,
+                                    out_existed, counters, &F, &arm, placed, st));
+    c->arm_seq += (unsigned long long)n;  // arm order = track call order, then array index
+    return OWGS_OK;
+}
+
 // ns = null: every item without a namespace (owgs_track_activations); invoker = null: nothing armed (the untimed calls)
 static int track_impl(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* action, const int32_t* ns,
                       const int32_t* ticket, int32_t* out_ticket, uint8_t* out_existed,
@@ -3771,31 +3830,20 @@ static int track_impl(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* 
     HIPCHK(c, upload(c->k_act, action, (size_t)n, c->stream));
     HIPCHK(c, upload(c->k_r0, ticket, (size_t)n, c->stream));
     HIPCHK(c, c->k_key.reserve((size_t)n));
-    HIPCHK(c, c->k_slot.reserve((size_t)n));
-    HIPCHK(c, c->k_state.reserve((size_t)n));
     HIPCHK(c, c->k_tick.reserve((size_t)n));
     HIPCHK(c, c->k_oflags.reserve((size_t)n));
     if (ns) HIPCHK(c, upload(c->k_r1, ns, (size_t)n, c->stream));
-    OwgsArm arm{};
-    arm.seq_base = c->arm_seq;
     if (invoker) {
         HIPCHK(c, upload(c->x_inv, invoker, (size_t)n, c->stream));
         HIPCHK(c, upload(c->x_tl, (const long long*)time_limit_ms, (size_t)n, c->stream));
-        arm.inv = c->x_inv.p;
-        arm.tl = c->x_tl.p;
-        arm.now = now_ms;
-        arm.std_ms = c->a_std;
-        arm.factor = c->a_factor;
-        arm.addon = c->a_addon;
     }
     HIPCHK(c, c->k_cnt.reserve(OWGS_CNT_WORDS));
     HIPCHK(c, hipMemsetAsync(c->k_cnt.p, 0, OWGS_CNT_WORDS * 8, c->stream));
     HIPCHK(c, owgs_launch_aid_decode(c->k_aid.p, n, nullptr, c->k_key.p, nullptr, nullptr, nullptr, c->stream));
-    OwgsActTable T = act_table(c);
-    const OwgsInflight F = inflight_args(c);
-    HIPCHK(c, owgs_launch_act_track(&T, c->k_key.p, n, c->k_act.p, ns ? c->k_r1.p : nullptr, c->k_r0.p, c->k_slot.p,
-                                    c->k_state.p, c->k_tick.p, c->k_oflags.p, c->k_cnt.p, &F, &arm, c->stream));
-    c->arm_seq += (unsigned long long)n;  // arm order = track call order, then array index
+    rc = track_device(c, n, c->k_key.p, c->k_act.p, ns ? c->k_r1.p : nullptr, c->k_r0.p,
+                      invoker ? c->x_inv.p : nullptr, invoker ? c->x_tl.p : nullptr, now_ms, nullptr, c->k_tick.p,
+                      c->k_oflags.p, c->k_cnt.p, c->stream);
+    if (rc) return rc;
     unsigned long long cnt[OWGS_CNT_WORDS];
     HIPCHK(c, hipMemcpyAsync(out_ticket, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(out_existed, c->k_oflags.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
@@ -4782,10 +4830,9 @@ static int msg_templates_upload(owgs_ctx* c, hipStream_t st) {
     return OWGS_OK;
 }
 
-// plan + write with device pointers; host-visible *total / *m
-static int msg_run(owgs_ctx* c, OwgsMsgArgs& A, int32_t n_topics, hipStream_t st, int64_t* total, int32_t* m) {
-    int rc = msg_templates_upload(c, st);
-    if (rc) return rc;
+// plan + write with device pointers, queued on st without a wait.  The templates are on the device already
+// (msg_templates_upload, which may wait).
+static int msg_queue(owgs_ctx* c, OwgsMsgArgs& A, int32_t n_topics, hipStream_t st) {
     const int32_t n = A.n;
     A.ta = c->m_ta.p;
     A.ta_off = c->m_ta_off.p;
@@ -4813,57 +4860,76 @@ static int msg_run(owgs_ctx* c, OwgsMsgArgs& A, int32_t n_topics, hipStream_t st
     HIPCHK(c, owgs_launch_msg_plan(&A, bits, c->m_temp.p, tb, c->m_key_sorted.p, c->m_iota.p, c->m_len_sorted.p,
                                    c->m_cnt.p, st));
     HIPCHK(c, owgs_launch_msg_write(&A, st));
-    int32_t bad = 0, mm = 0;
-    int64_t tot = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, c->m_bad.p, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&mm, A.topic_start + n_topics, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&tot, A.out_off + n, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (total) *total = tot;
-    if (m) *m = mm;
+    return OWGS_OK;
+}
+
+// the message stage's verdict from its bad-input word
+static int msg_verdict(owgs_ctx* c, int32_t bad) {
     if (bad & 1) return c->fail(OWGS_EINVAL, "serialize: invoker >= n_topics or unknown template");
     if (bad & 2) return c->fail(OWGS_EINVAL, "serialize: transaction id is not valid UTF-8");
     if (bad & 4) return c->fail(OWGS_ERANGE, "serialize: output capacity below the batch's bytes (see *total)");
     return OWGS_OK;
 }
 
-static bool msg_batch_ok(const owgs_msg_batch* b, int32_t n_topics) {
-    if (!b || b->n < 0 || n_topics < 0 || n_topics >= INT32_MAX) return false;
-    if (b->n == 0) return true;
-    return b->invoker && b->tmpl && b->aid && b->tid_off && b->tid_start && b->flags;
+// queue + finish: host-visible *total / *m (one wait)
+static int msg_run(owgs_ctx* c, OwgsMsgArgs& A, int32_t n_topics, hipStream_t st, int64_t* total, int32_t* m) {
+    int rc = msg_templates_upload(c, st);
+    if (!rc) rc = msg_queue(c, A, n_topics, st);
+    if (rc) return rc;
+    int32_t bad = 0, mm = 0;
+    int64_t tot = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, c->m_bad.p, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&mm, A.topic_start + n_topics, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&tot, A.out_off + A.n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (total) *total = tot;
+    if (m) *m = mm;
+    return msg_verdict(c, bad);
 }
 
-int owgs_serialize_activations(owgs_ctx* c, const owgs_msg_batch* b, int32_t n_topics, char* out, int64_t cap,
-                               int64_t* out_off, int32_t* out_order, int32_t* topic_start, int64_t* total,
-                               int32_t* m) {
-    if (!c || !msg_batch_ok(b, n_topics) || cap < 0 || !out_off || !topic_start || (b->n > 0 && !out_order) ||
+// fused: the batch of owgs_publish_activations, whose invoker and aid are the call's own (both must be NULL)
+static bool msg_batch_ok(const owgs_msg_batch* b, int32_t n_topics, bool fused = false) {
+    if (!b || b->n < 0 || n_topics < 0 || n_topics >= INT32_MAX) return false;
+    if (fused && (b->invoker || b->aid)) return false;
+    if (b->n == 0) return true;
+    return (fused || (b->invoker && b->aid)) && b->tmpl && b->tid_off && b->tid_start && b->flags;
+}
+
+struct MsgNeeds {
+    bool c = false, r = false, x = false;  // some flag asks for content / traceContext / cause
+};
+
+// the host-side checks of a batch in host buffers and of its outputs, before anything is touched
+static int msg_host_check(owgs_ctx* c, const owgs_msg_batch* b, int32_t n_topics, const char* out, int64_t cap,
+                          const int64_t* out_off, const int32_t* out_order, const int32_t* topic_start, bool fused,
+                          MsgNeeds& need) {
+    if (!c || !msg_batch_ok(b, n_topics, fused) || cap < 0 || !out_off || !topic_start || (b->n > 0 && !out_order) ||
         (cap > 0 && !out))
         return OWGS_EINVAL;
     const int32_t n = b->n;
     if (n > 0 && b->tid_off[n] > b->tid_off[0] && !b->tid)
         return c->fail(OWGS_EINVAL, "serialize: transaction id bytes missing");
-    bool need_c = false, need_r = false, need_x = false;
     for (int32_t i = 0; i < n; ++i) {
-        need_c |= (b->flags[i] & OWGS_MSG_HAS_CONTENT) != 0;
-        need_x |= (b->flags[i] & OWGS_MSG_HAS_CAUSE) != 0;
-        need_r |= (b->flags[i] & OWGS_MSG_HAS_TRACE) != 0;
+        need.c |= (b->flags[i] & OWGS_MSG_HAS_CONTENT) != 0;
+        need.x |= (b->flags[i] & OWGS_MSG_HAS_CAUSE) != 0;
+        need.r |= (b->flags[i] & OWGS_MSG_HAS_TRACE) != 0;
     }
-    if ((need_c && (!b->content || !b->content_off)) || (need_x && !b->cause) || (need_r && (!b->trace || !b->trace_off)))
+    if ((need.c && (!b->content || !b->content_off)) || (need.x && !b->cause) ||
+        (need.r && (!b->trace || !b->trace_off)))
         return c->fail(OWGS_EINVAL, "serialize: a flag asks for content / cause / traceContext that is missing");
     for (int32_t i = 0; i < n; ++i)
-        if (b->tid_off[i + 1] < b->tid_off[i] || (need_c && b->content_off[i + 1] < b->content_off[i]) ||
-            (need_r && b->trace_off[i + 1] < b->trace_off[i]))
+        if (b->tid_off[i + 1] < b->tid_off[i] || (need.c && b->content_off[i + 1] < b->content_off[i]) ||
+            (need.r && b->trace_off[i + 1] < b->trace_off[i]))
             return c->fail(OWGS_EINVAL, "serialize: offsets must be non-decreasing");
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    hipStream_t st = c->stream;
+    return OWGS_OK;
+}
+
+// a checked host batch -> the context's device buffers, outputs reserved; A is complete but for invoker and aid
+static int msg_upload(owgs_ctx* c, const owgs_msg_batch* b, const MsgNeeds& need, int32_t n_topics, int64_t cap,
+                      OwgsMsgArgs& A, hipStream_t st) {
+    const int32_t n = b->n;
     const int64_t tid0 = n ? b->tid_off[0] : 0, tidn = n ? b->tid_off[n] : 0;
-    HIPCHK(c, upload(c->m_inv, b->invoker, (size_t)n, st));
     HIPCHK(c, upload(c->m_tmpl, b->tmpl, (size_t)n, st));
-    HIPCHK(c, upload(c->m_aid, (const ulonglong2*)b->aid, (size_t)n, st));
     HIPCHK(c, upload(c->m_tid, b->tid + tid0, (size_t)(tidn - tid0), st));
     std::vector<int64_t> off((size_t)n + 1);
     for (int32_t i = 0; i <= n; ++i) off[i] = n ? b->tid_off[i] - tid0 : 0;
@@ -4871,17 +4937,17 @@ int owgs_serialize_activations(owgs_ctx* c, const owgs_msg_batch* b, int32_t n_t
     HIPCHK(c, upload(c->m_tid_start, b->tid_start, (size_t)n, st));
     HIPCHK(c, upload(c->m_flags, b->flags, (size_t)n, st));
     std::vector<int64_t> coff((size_t)n + 1, 0), roff((size_t)n + 1, 0);
-    if (need_c) {
+    if (need.c) {
         for (int32_t i = 0; i <= n; ++i) coff[i] = b->content_off[i] - b->content_off[0];
         HIPCHK(c, upload(c->m_content, b->content + b->content_off[0], (size_t)coff[n], st));
     }
-    if (need_r) {
+    if (need.r) {
         for (int32_t i = 0; i <= n; ++i) roff[i] = b->trace_off[i] - b->trace_off[0];
         HIPCHK(c, upload(c->m_trace, b->trace + b->trace_off[0], (size_t)roff[n], st));
     }
     HIPCHK(c, upload(c->m_content_off, coff.data(), coff.size(), st));
     HIPCHK(c, upload(c->m_trace_off, roff.data(), roff.size(), st));
-    if (need_x) HIPCHK(c, upload(c->m_cause, (const ulonglong2*)b->cause, (size_t)n, st));
+    if (need.x) HIPCHK(c, upload(c->m_cause, (const ulonglong2*)b->cause, (size_t)n, st));
     else HIPCHK(c, c->m_cause.reserve(1));
     HIPCHK(c, c->m_content.reserve(1));
     HIPCHK(c, c->m_trace.reserve(1));
@@ -4889,11 +4955,8 @@ int owgs_serialize_activations(owgs_ctx* c, const owgs_msg_batch* b, int32_t n_t
     HIPCHK(c, c->m_out_off.reserve((size_t)n + 1));
     HIPCHK(c, c->m_topic.reserve((size_t)n_topics + 1));
     HIPCHK(c, c->m_out.reserve((size_t)std::max<int64_t>(cap, 1)));
-    OwgsMsgArgs A{};
     A.n = n;
-    A.invoker = c->m_inv.p;
     A.tmpl = c->m_tmpl.p;
-    A.aid = c->m_aid.p;
     A.tid = c->m_tid.p;
     A.tid_off = c->m_tid_off.p;
     A.tid_start = c->m_tid_start.p;
@@ -4908,18 +4971,47 @@ int owgs_serialize_activations(owgs_ctx* c, const owgs_msg_batch* b, int32_t n_t
     A.topic_start = c->m_topic.p;
     A.out = c->m_out.p;
     A.cap = cap;
-    int64_t tot = 0;
-    int32_t mm = 0;
-    int rc = msg_run(c, A, n_topics, st, &tot, &mm);
-    if (total) *total = tot;
-    if (m) *m = mm;
-    if (rc) return rc;
+    return OWGS_OK;
+}
+
+// the serialised batch (tot bytes, mm messages) from the context's device buffers into the caller's; waits
+static int msg_download(owgs_ctx* c, int32_t n_topics, int64_t tot, int32_t mm, char* out, int64_t* out_off,
+                        int32_t* out_order, int32_t* topic_start, hipStream_t st) {
     if (tot) HIPCHK(c, hipMemcpyAsync(out, c->m_out.p, (size_t)tot, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(out_off, c->m_out_off.p, (size_t)(mm + 1) * 8, hipMemcpyDeviceToHost, st));
     if (mm) HIPCHK(c, hipMemcpyAsync(out_order, c->m_order.p, (size_t)mm * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(topic_start, c->m_topic.p, (size_t)(n_topics + 1) * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     return OWGS_OK;
+}
+
+int owgs_serialize_activations(owgs_ctx* c, const owgs_msg_batch* b, int32_t n_topics, char* out, int64_t cap,
+                               int64_t* out_off, int32_t* out_order, int32_t* topic_start, int64_t* total,
+                               int32_t* m) {
+    MsgNeeds need;
+    int rc = msg_host_check(c, b, n_topics, out, cap, out_off, out_order, topic_start, false, need);
+    if (rc) return rc;
+    const int32_t n = b->n;
+    OWGS_ENTER(c);
+    {
+        const int ro_ = order_on(c, c->stream);
+        if (ro_) return ro_;
+    }
+    hipStream_t st = c->stream;
+    HIPCHK(c, upload(c->m_inv, b->invoker, (size_t)n, st));
+    HIPCHK(c, upload(c->m_aid, (const ulonglong2*)b->aid, (size_t)n, st));
+    OwgsMsgArgs A{};
+    rc = msg_upload(c, b, need, n_topics, cap, A, st);
+    if (rc) return rc;
+    A.invoker = c->m_inv.p;
+    A.aid = c->m_aid.p;
+    int64_t tot = 0;
+    int32_t mm = 0;
+    rc = msg_run(c, A, n_topics, st, &tot, &mm);
+    if (total) *total = tot;
+    if (m) *m = mm;
+    if (rc) return rc;
+    return msg_download(c, n_topics, tot, mm, out, out_off, out_order, topic_start, st);
 }
 
 int owgs_serialize_activations_device(owgs_ctx* c, const owgs_msg_batch* b, int32_t n_topics, char* out,
@@ -4957,6 +5049,157 @@ int owgs_serialize_activations_device(owgs_ctx* c, const owgs_msg_batch* b, int3
     A.out = out;
     A.cap = cap;
     return msg_run(c, A, n_topics, st, total, m);
+}
+
+// ------------------------------------------------------------------------------------------ publish end to end
+// ShardingContainerPoolBalancer.publish (SCPB:257-317) for a drained batch: schedule, setupActivation for the placed
+// items, the serialised messages -- the decisions never leave the device between the stages.  On an
+// on-chip context nothing below waits between queueing the engine and the one block copy; the gate kernel reads the
+// error word on the device, so an engine error leaves the later stages with nothing to do.
+int owgs_publish_activations(owgs_ctx* c, const owgs_publish_io* io, const owgs_msg_batch* msgs, owgs_msg_out* mo,
+                             int64_t out_summary[8]) {
+    if (!c || !io || !out_summary) return OWGS_EINVAL;
+    const int32_t n = io->n;
+    if (n < 0 || (msgs == nullptr) != (mo == nullptr)) return OWGS_EINVAL;
+    if (n > 0 && (!io->action || !io->aid || !io->ticket || !io->time_limit_ms || !io->out_invoker ||
+                  !io->out_flags || !io->out_ticket || !io->out_existed))
+        return OWGS_EINVAL;
+    MsgNeeds need;
+    if (msgs) {
+        if (msgs->n != n) return c->fail(OWGS_EINVAL, "publish: msgs->n differs from io->n");
+        const int rm = msg_host_check(c, msgs, mo->n_topics, mo->out, mo->cap, mo->out_off, mo->out_order,
+                                      mo->topic_start, true, need);
+        if (rm) return rm;
+    }
+    if (io->now_ms < 0 || io->now_ms >= (1LL << 60)) return c->fail(OWGS_EINVAL, "publish: now outside [0, 2^60)");
+    for (int32_t i = 0; i < n; ++i)
+        if (io->time_limit_ms[i] < 0 || io->time_limit_ms[i] >= (1LL << 40))
+            return c->fail(OWGS_EINVAL, "publish: time limit outside [0, 2^40)");
+    if (!registered(c, n, io->action)) return c->fail(OWGS_ENOENT, "unknown action");
+    if (io->ns) {
+        const int32_t nn = (int32_t)c->ns_map.size();
+        for (int32_t i = 0; i < n; ++i)
+            if (io->ns[i] != OWGS_NONE && (io->ns[i] < 0 || io->ns[i] >= nn))
+                return c->fail(OWGS_ENOENT, "unknown namespace");
+    }
+    for (int k = 0; k < 8; ++k) out_summary[k] = 0;
+    if (n == 0) {
+        if (mo) {
+            mo->total = 0;
+            mo->m = 0;
+            mo->out_off[0] = 0;
+            for (int32_t k = 0; k <= mo->n_topics; ++k) mo->topic_start[k] = 0;
+            out_summary[6] = 3;
+        } else {
+            out_summary[6] = 2;
+        }
+        return OWGS_OK;
+    }
+    OWGS_ENTER(c);
+    {
+        const int ro_ = order_on(c, c->stream);
+        if (ro_) return ro_;
+    }
+    hipStream_t st = c->stream;
+    // everything that may wait comes first: the table's rehash, the templates, the buffers
+    int rc = act_reserve(c, n);
+    if (!rc && msgs) rc = msg_templates_upload(c, st);
+    if (rc) return rc;
+    const size_t hdr_bytes = (size_t)OWGS_PUB_HDR * 8, blk_bytes = hdr_bytes + (size_t)n * 10;
+    if (c->p_pin_bytes < blk_bytes) {
+        if (c->p_pin) (void)hipHostFree(c->p_pin);
+        c->p_pin = nullptr;
+        c->p_pin_bytes = 0;
+        HIPCHK(c, hipHostMalloc(&c->p_pin, blk_bytes * 2, hipHostMallocDefault));
+        c->p_pin_bytes = blk_bytes * 2;
+    }
+    HIPCHK(c, c->p_blk.reserve(blk_bytes));
+    HIPCHK(c, c->p_placed.reserve((size_t)n));
+    if (msgs) HIPCHK(c, c->p_minv.reserve((size_t)n));
+    // stage 1: the decisions, left in d_out / d_flags (the action handles in d_a)
+    rc = publish_device(c, n, io->action, io->seq, io->seq_base, nullptr, nullptr);
+    if (rc) return rc;  // (only the large-state engine reports its own error here: nothing is tracked or written)
+    // the inputs of stages 2 and 3 go up while the engine runs
+    HIPCHK(c, upload(c->k_key, (const ulonglong2*)io->aid, (size_t)n, st));
+    HIPCHK(c, upload(c->k_r0, io->ticket, (size_t)n, st));
+    if (io->ns) HIPCHK(c, upload(c->k_r1, io->ns, (size_t)n, st));
+    HIPCHK(c, upload(c->x_tl, (const long long*)io->time_limit_ms, (size_t)n, st));
+    OwgsMsgArgs A{};
+    if (msgs) {
+        rc = msg_upload(c, msgs, need, mo->n_topics, mo->cap, A, st);
+        if (rc) return rc;
+    }
+    unsigned long long* hdr = (unsigned long long*)c->p_blk.p;
+    int32_t* b_inv = (int32_t*)(c->p_blk.p + hdr_bytes);
+    int32_t* b_tick = b_inv + n;
+    uint8_t* b_flags = (uint8_t*)(b_tick + n);
+    uint8_t* b_ex = b_flags + n;
+    HIPCHK(c, hipMemsetAsync(hdr, 0, hdr_bytes, st));
+    OwgsPublishGate G{};
+    G.n = n;
+    G.err = c->d_err.p;
+    G.dec = c->d_out.p;
+    G.dflags = c->d_flags.p;
+    G.action = c->d_a.p;
+    G.act_bb = c->d_act_bb.p;
+    G.placed = c->p_placed.p;
+    G.msg_inv = msgs ? c->p_minv.p : nullptr;
+    G.hdr = hdr;
+    G.out_inv = b_inv;
+    G.out_ticket = b_tick;
+    G.out_flags = b_flags;
+    G.out_existed = b_ex;
+    HIPCHK(c, owgs_launch_publish_gate(&G, st));
+    // stage 2: setupActivation of the placed items, the entry's invoker read from the decisions
+    rc = track_device(c, n, c->k_key.p, c->d_a.p, io->ns ? c->k_r1.p : nullptr, c->k_r0.p, c->d_out.p, c->x_tl.p,
+                      io->now_ms, c->p_placed.p, b_tick, b_ex, hdr + OWGS_PUB_CNT, st);
+    if (rc) return rc;
+    // stage 3: the messages of the placed items
+    if (msgs) {
+        A.invoker = c->p_minv.p;
+        A.aid = c->k_key.p;
+        rc = msg_queue(c, A, mo->n_topics, st);
+        if (rc) return rc;
+        HIPCHK(c, owgs_launch_publish_collect(hdr, c->m_bad.p, A.topic_start, mo->n_topics, A.out_off, n, st));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->p_pin, c->p_blk.p, blk_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const unsigned long long* H = (const unsigned long long*)c->p_pin;
+    if (H[OWGS_PUB_ERR]) {  // the engine failed: the gate placed nothing, the table and the books are untouched
+        rc = check_err_word(c);
+        return rc ? rc : c->fail(OWGS_EDEVICE, "publish: the engine's error word was set");
+    }
+    const char* P = (const char*)c->p_pin + hdr_bytes;
+    memcpy(io->out_invoker, P, (size_t)n * 4);
+    memcpy(io->out_ticket, P + (size_t)n * 4, (size_t)n * 4);
+    memcpy(io->out_flags, P + (size_t)n * 8, (size_t)n);
+    memcpy(io->out_existed, P + (size_t)n * 9, (size_t)n);
+    const long long placed = (long long)H[OWGS_PUB_PLACED], inserted = (long long)H[OWGS_PUB_CNT + OWGS_CNT_INSERTED];
+    c->t_used += inserted;
+    c->t_live += inserted;
+    // CLB:121-125 for every placed item, duplicates included; an item without an invoker never reaches them
+    c->f_total += placed;
+    c->f_mb_managed += (long long)H[OWGS_PUB_CNT + OWGS_CNT_MANAGED_MB];
+    c->f_mb_blackbox += (long long)H[OWGS_PUB_CNT + OWGS_CNT_BLACKBOX_MB];
+    out_summary[0] = placed;
+    out_summary[1] = inserted;
+    out_summary[2] = (int64_t)H[OWGS_PUB_OVL_MANAGED];
+    out_summary[3] = (int64_t)H[OWGS_PUB_OVL_BLACKBOX];
+    out_summary[4] = (int64_t)H[OWGS_PUB_NONE];
+    out_summary[5] = (int64_t)H[OWGS_PUB_THROW];
+    out_summary[6] = 2;
+    for (int32_t i = 0; i < n; ++i)
+        if (io->out_existed[i] == 2) return c->fail(OWGS_EDEVICE, "publish: activation table full");
+    if (!msgs) return OWGS_OK;
+    const int32_t mm = (int32_t)H[OWGS_PUB_MSG_M];
+    const int64_t tot = (int64_t)H[OWGS_PUB_MSG_TOTAL];
+    mo->total = tot;
+    mo->m = mm;
+    rc = msg_verdict(c, (int32_t)H[OWGS_PUB_MSG_BAD]);
+    if (!rc) rc = msg_download(c, mo->n_topics, tot, mm, mo->out, mo->out_off, mo->out_order, mo->topic_start, st);
+    if (rc) return rc;  // the entries stay, left to their timeouts (SCPB:302-303): serialise again with out_invoker
+    out_summary[6] = 3;
+    return OWGS_OK;
 }
 
 int owgs_resident_stats(owgs_ctx* c, int64_t* out, int32_t cap) {

@@ -641,6 +641,36 @@ struct OwgsInflight {
     const uint8_t* act_bb;       // action.exec.pull by action handle
 };
 
+// owgs_publish_activations (owgs_publish.hip): the gate between the engine and the table kernels.  The call's outputs
+// leave the device as ONE block: OWGS_PUB_HDR 64-bit header words, then out_invoker [n] and out_ticket [n] (int32),
+// then out_flags [n] and out_existed [n] (bytes).
+#define OWGS_PUB_PLACED 0        // header words [0..4]: the gate's ballot counts (out_summary [0], [2], [3], [4], [5])
+#define OWGS_PUB_OVL_MANAGED 1
+#define OWGS_PUB_OVL_BLACKBOX 2
+#define OWGS_PUB_NONE 3
+#define OWGS_PUB_THROW 4
+#define OWGS_PUB_ERR 5           // the context's error word as the gate saw it
+#define OWGS_PUB_MSG_BAD 6       // message stage: the bad-input word, the message count and the bytes needed
+#define OWGS_PUB_MSG_M 7
+#define OWGS_PUB_MSG_TOTAL 8
+#define OWGS_PUB_CNT 12          // [12..15]: the table kernels' OWGS_CNT_* words
+#define OWGS_PUB_HDR 16
+struct OwgsPublishGate {
+    int32_t n;
+    const int32_t* err;          // the context's error word (set by the engine): non-zero suppresses every item
+    const int32_t* dec;          // [n] the engine's decisions
+    const uint8_t* dflags;       // [n] ... and overload flags
+    const int32_t* action;       // [n] action handles
+    const uint8_t* act_bb;       // action.exec.pull by handle
+    uint8_t* placed;             // out [n]: 1 = setupActivation runs for the item (SCPB:292-304)
+    int32_t* msg_inv;            // out [n] or null: the decision of a placed item, -1 otherwise (the message stage's input)
+    unsigned long long* hdr;     // the block's header (zero before the launch)
+    int32_t* out_inv;            // block arrays: copies of dec / dflags, and -1 / 0 for the items that are not placed
+    int32_t* out_ticket;
+    uint8_t* out_flags;
+    uint8_t* out_existed;
+};
+
 struct OwgsAckCompleteArgs {
     const ulonglong2* key;
     const uint8_t* info;

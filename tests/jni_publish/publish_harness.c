@@ -1,0 +1,16 @@
+/*
+ * publish_harness.c -- the publishActivations native of integration/owgs_jni.c executed without a JVM
+ * (tests/test_gpu_publish_jni.py).
+ *
+ * The JNIEnv stand-in, its Java-object stand-ins and the ctypes surface for creating objects and contexts are
+ * tests/jni_stub/jni_harness.c's, compiled into this library unchanged by including it; only the h_* wrapper below is
+ * new.  integration/Makefile builds it as integration/build/libowgs_jni_publish_harness.so.
+ */
+#include "../jni_stub/jni_harness.c"
+
+jint JN(publishActivations)(JNIEnv*, jobject, jlong, jobject, jobject, jint, jboolean, jlong, jlong);
+
+HX int32_t h_publish_activations(int64_t h, void* in, void* out, int32_t n, int32_t has_ns, int64_t seq_base,
+                                 int64_t now_ms) {
+    return JN(publishActivations)(&g_env, NULL, h, in, out, n, (jboolean)(has_ns != 0), seq_base, now_ms);
+}
