@@ -82,6 +82,12 @@ typedef unsigned long long u64;
 #ifndef OWGS_EXT
 #define OWGS_EXT 1  // stopping maxConcurrent == 1 lanes are re-decided exactly inside the pass (see the commit phase)
 #endif
+#ifndef OWGS_COOP_GIVEBACK
+#define OWGS_COOP_GIVEBACK 1  // before the re-decisions the engine lanes give their own takes back (0: the I/O wave, from fxa)
+#endif
+#ifndef OWGS_COOP_CLASH
+#define OWGS_COOP_CLASH 1  // after the re-decisions the lanes that stay test themselves against the re-decided sets (0: the I/O wave marks them in fxa)
+#endif
 #ifndef EXT_MAX
 #define EXT_MAX 48  // re-decisions per pass
 #endif
@@ -2795,12 +2801,23 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                 const int l0 = l;
                 // (the first stop must be re-decidable, else the pass ends as before)
                 const bool fixup = l < len && (fxa[l].x & FX_OK);
+                auto hsh = [](uint32_t v) { return (v * 2654435761u) >> 21; };  // bit of a value in a 2048-bit set
                 if (fixup) {
+#if OWGS_COOP_GIVEBACK
+                    // every lane from l on gives its tentative take back itself (one LDS add from its registers: what
+                    // it took in the tentative phase): the permits are then exactly what lane l sees (the frontier
+                    // minus the lanes before it); the lanes that commit add theirs again below.  l and fixup are
+                    // uniform (read from LDS after barrier 4; the I/O wave writes fxa only after this barrier), so
+                    // every wave of both roles reaches it
+                    if (!io && part && li >= l && cons) atomicAdd(&P[t], cons);
+                    LDS_SYNC_T(10);
+#endif
                     if (io) {
 #ifdef OWGS_EXT_PROF
                         const u64 tx0 = memtime_pinned();
                         u64 tq_prev = tx0;
 #endif
+#if !OWGS_COOP_GIVEBACK
                         // every lane from l on gives its tentative take back: the permits are then exactly what lane l
                         // sees (the frontier minus the lanes before it); the lanes that commit add theirs again below
                         for (int k0 = l; k0 < len; k0 += 64) {
@@ -2810,10 +2827,10 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                 if (f2.w >> 31) atomicAdd(&P[(int)(f2.y & 0xFFFFu)], (int)(f2.w & OWGS_AM_MEM_MASK));
                             }
                         }
+#endif
                         int L = l, nE = 0;
                         // the re-decided lanes' targets and actions as hashed 2048-bit sets over the wave's lanes
                         uint32_t set_t = 0u, set_a = 0u;
-                        auto hsh = [](uint32_t v) { return (v * 2654435761u) >> 21; };
                         auto inset = [&](uint32_t bits, uint32_t h) {  // (whole wave: ds_bpermute)
                             return ((uint32_t)__shfl((int)bits, (int)(h >> 5), 64) >> (h & 31u)) & 1u;
                         };
@@ -2973,6 +2990,15 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                         // lanes from the limit on that meet a re-decided lane's target or action must speculate again
                         // (their validation assumed the re-decided lanes where they speculated: a kept one would
                         // keep a target whose room is gone or a rank that no longer holds)
+#if OWGS_COOP_CLASH
+                        // (each such lane tests itself after barrier 9: the two sets go to LDS, one word per lane, in
+                        // the long-walk queue's first 512 bytes -- dead from barrier 3 to the next pass's speculation,
+                        // and the pre-walk results it holds in OWGS_PRE builds were last read by the loop above)
+                        if (nE > 0) {
+                            ((uint32_t*)lq)[lane] = set_t;
+                            ((uint32_t*)lq)[64 + lane] = set_a;
+                        }
+#else
                         if (nE > 0)
                             for (int k0 = L; k0 < len; k0 += 64) {
                                 const int k = k0 + lane;
@@ -2981,6 +3007,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                 const bool cl = (inset(set_a, hsh(f2.x & OWGS_REC_NOACT)) | inset(set_t, hsh(f2.y & 0xFFFFu))) != 0u;
                                 if (k < len && !(f2.x & (FX_EXEMPT | FX_DONE)) && cl) fxa[k].x = f2.x | FX_CLASH;
                             }
+#endif
                         st_ext += (uint32_t)nE;
 #ifdef OWGS_EXT_PROF
                         xp_cyc += memtime_pinned() - tx0;
@@ -3106,7 +3133,16 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                 if (act && li >= l) {
                     keep = !nf;
 #if OWGS_EXT
+#if OWGS_COOP_CLASH
+                    // (not exempt, never re-decided: li >= l) its own target and action against the published sets
+                    if (keep && fixup && part && kind != K_FALLBACK && sc[SC_NEXT] > 0) {
+                        const uint32_t h1 = hsh((uint32_t)t), h2 = hsh((uint32_t)a);
+                        const uint32_t* sw = (const uint32_t*)lq;
+                        if (((sw[h1 >> 5] >> (h1 & 31u)) | (sw[64 + (h2 >> 5)] >> (h2 & 31u))) & 1u) keep = false;
+                    }
+#else
                     if (keep && fixup && sc[SC_NEXT] > 0 && (fxa[li].x & FX_CLASH)) keep = false;
+#endif
 #endif
                     if (!keep && hs >= 0) hflag[hs] = l;  // the action's hot table is needed in the next pass
                     if (!keep && maxc > 1) cdirty[(par ^ 1) * OWGS_WL + lead] = 1;

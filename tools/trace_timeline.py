@@ -1,7 +1,8 @@
 """Diagnostic: analyse a barrier timeline written by a -DOWGS_TRACE engine (env OWGS_TRACE_FILE).
 
 For every pass-loop barrier (1 chunk start, 8 after the hot-action and per-lane walks, 2 after the queued long walks,
-3 after tentative consumption, 4 before commit, 5 end of pass) and every wave: cycles from the previous barrier's departure to this arrival (the wave's own work),
+3 after tentative consumption, 4 before commit, 10 after the lanes' give-back and 9 after the in-pass re-decisions in
+a pass that has them, 5 end of pass) and every wave: cycles from the previous barrier's departure to this arrival (the wave's own work),
 which wave arrived last (the critical path), and the barrier's own cost (last arrival -> departure)."""
 import sys
 
@@ -20,7 +21,9 @@ assert (ids == ids[0]).all(), "waves disagree on the barrier sequence"
 # a phase is named after what runs before the barrier that ends it: barrier 8 ends the hot-action and per-lane walks
 # (and the long-walk queue's push), barrier 2 the queued long walks (round 3's files used the two names swapped)
 names = {1: "chunk_start", 2: "long walks", 3: "tentative", 4: "validate", 5: "commit", 8: "speculate",
-         6: "(mark) chunk loop", 7: "(mark) lane decode", 9: "re-decisions"}
+         6: "(mark) chunk loop", 7: "(mark) lane decode", 9: "re-decisions",
+         # 10 ends the engine lanes' give-back before the re-decisions (row 9 is then the I/O wave's loop alone)
+         10: "give-back"}
 work = ta[:, 1:] - td[:, :-1]  # per wave: departure of barrier k-1 -> arrival at barrier k
 crit = work.max(axis=0)
 last = work.argmax(axis=0)
