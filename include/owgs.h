@@ -243,7 +243,8 @@ int owgs_replay(owgs_ctx* ctx, int32_t n_batches, const int64_t* acq_off, const 
 #define OWGS_ACK_FAIL 0           /* AcknowledegmentMessage.parse fails (CLB:226-228): the shim logs the raw message */
 #define OWGS_ACK_JVM 1            /* the message has a "response" member (ResultMessage / Combined...): its
                                      WhiskActivation is deserialised by the JVM, which completes the slot with
-                                     owgs_complete_activations */
+                                     owgs_complete_activations.  From owgs_process_result_acks: only a message whose
+                                     `response` object lies outside the accepted subset */
 #define OWGS_ACK_UNSUPPORTED 2    /* outside the device parser's limits (container depth > 64, an exponent of more
                                      than 9 digits, a non-ASCII or numeric activation id, U+FFFF, a number of more
                                      than 34 significant digits in instance / transid): the JVM parses it */
@@ -512,13 +513,87 @@ int owgs_process_pings(owgs_ctx* ctx, int32_t n, const char* bytes, const int64_
  * (CLB:328-345); an id without an actor is ignored by the FSM as by InvokerPool (ISUP:135-137).  now_ms before the
  * FSM's last now_ms or outside [0, 2^60) is OWGS_EINVAL before any ack is processed.  A batch that feeds no event
  * leaves the FSM's clock alone, as the expiry sweep does.  Messages reported OWGS_ACK_JVM are completed by the shim
- * through owgs_complete_activations_supervised once the JVM has parsed them. */
+ * through owgs_complete_activations_supervised once the JVM has parsed them (owgs_process_result_acks below completes
+ * most of them in the batch itself). */
 int owgs_process_acks_supervised(owgs_ctx* ctx, int32_t n, const char* bytes, const int64_t* off, uint8_t* out_kind,
                                  int32_t* out_invoker, int32_t* out_ticket, uint8_t* out_flags, int64_t now_ms,
                                  int32_t apply, int32_t out_summary[3]);
 int owgs_complete_activations_supervised(owgs_ctx* ctx, int32_t n, const char* aid32, const int32_t* invoker,
                                          const uint8_t* flags, uint8_t* out_kind, int32_t* out_ticket,
                                          uint8_t* out_flags, int64_t now_ms, int32_t apply, int32_t out_summary[3]);
+
+/* ---- result-carrying acks: CombinedCompletionAndResultMessage and ResultMessage on the device -------------------
+ * Completes the dispatch of AcknowledegmentMessage.serdes.read (Message.scala:240-258): owgs_process_acks* hand every
+ * message with a `response` member to the JVM (OWGS_ACK_JVM); this call classifies them too, so that a controller
+ * serving blocking invokes (ContainerProxy.scala:768-781 sends a Combined message for each unless split acks are
+ * configured) needs one device call per ack batch and no ActivationId -> Promise map beside activationSlots. */
+#define OWGS_ACK_RESULT 7    /* out_kind: an accepted ResultMessage: processResult only, nothing completed */
+#define OWGS_ACKF_RESULT 8   /* out_flags bit3: the message carries a result (processResult runs, CLB:218-220) */
+#define OWGS_ACKF_RIGHT 16   /* out_flags bit4: response is a WhiskActivation object (Right); clear: an id (Left) */
+typedef struct owgs_ack_out {
+    uint8_t* kind; int32_t* invoker; int32_t* ticket; uint8_t* flags;
+    uint64_t* aid;        /* 2n words (hi, lo) of acknowledgement.activationId, 0 when not parsed */
+    int64_t* resp_off;    /* start of the `response` value in bytes[], 0 when OWGS_ACKF_RESULT is clear */
+    int32_t* resp_len;    /* its length in bytes */
+} owgs_ack_out;
+/* With out_summary != NULL the feed, now_ms, apply and failure atomicity are those of owgs_process_acks_supervised.
+ * With out_summary == NULL nothing is fed; now_ms and apply must then be 0, else OWGS_EINVAL.  Argument errors (a NULL
+ * out or member with n > 0, offsets out of order, the feed's checks) return before anything runs.
+ *
+ * Messages are classified in array order, one per message; the grammar, its limits (OWGS_ACK_UNSUPPORTED) and the
+ * U+FFFF rule are those of owgs_process_acks.
+ *  1. No `response` member: exactly as by owgs_process_acks.  aid = the CompletionMessage's id when it is accepted
+ *     (RELEASED / HEALTH / NOENTRY), 0 otherwise.
+ *  2. A `response` member (the last top-level member of that name):
+ *     - a JSON string is Left(ActivationId) through ActivationId.serdes (ActivationId.scala:58-95) with the rules of
+ *       `activationId`: a wrong length or a non-hex character is OWGS_ACK_FAIL, a non-ASCII character
+ *       OWGS_ACK_UNSUPPORTED;
+ *     - a JSON object is Right(WhiskActivation) only inside the accepted subset below; any other object is
+ *       OWGS_ACK_JVM, as from owgs_process_acks: the device never reports an object as FAIL;
+ *     - any other value is OWGS_ACK_FAIL (Message.scala:236).
+ *  3. With an `invoker` member the message is a CombinedCompletionAndResultMessage (jsonFormat4: transid, response,
+ *     isSystemError, invoker; Message.scala:191-193).  transid must be present (TransactionId.serdes.read itself never
+ *     fails, TransactionId.scala:243-251), isSystemError is absent, null or a boolean, invoker an InvokerInstanceId as
+ *     in a CompletionMessage; health-transid detection is the CompletionMessage's.  A top-level `activationId` is
+ *     ignored: the id is the response's (Message.scala:125), the string or the object's `activationId`.  FAIL takes
+ *     precedence over UNSUPPORTED, JVM (an object outside the subset) over both.  An accepted Combined message is a
+ *     completion: outcome (RELEASED / HEALTH / NOENTRY), release flags, books, timeouts, watch refresh, large-state
+ *     branch and health event are exactly those of a CompletionMessage with the same id, invoker, isSystemError and
+ *     transid at the same array position.  In addition OWGS_ACKF_RESULT is set, OWGS_ACKF_RIGHT for an object, and
+ *     aid, resp_off and resp_len are written.
+ *  4. Without an `invoker` member the message is a ResultMessage (jsonFormat2: transid, response; Message.scala:221;
+ *     every other member is ignored).  Accepted: out_kind = OWGS_ACK_RESULT, invoker = -1, flags = OWGS_ACKF_RESULT
+ *     (| OWGS_ACKF_RIGHT), aid / resp_off / resp_len written; nothing is removed, released, counted or fed.
+ *     out_ticket = the ticket of the id's entry if that entry is live at the message's turn -- ready when the batch
+ *     starts and removed by no message at a lower index of this batch -- and -1 otherwise.  It is what processResult
+ *     (CLB:235-243) needs: a shim that keeps its promises by ticket needs no id map; out_aid covers the -1 cases.
+ *
+ * Accepted subset of a `response` object -- a sufficient condition for convertTo[WhiskActivation] (jsonFormat13,
+ * WhiskActivation.scala:52-64, 182) to succeed, not an exact one; the authoritative list:
+ *  - member names: no member name of the object, of its `response` object or of an annotation is written with an
+ *    escape; none of the 13 names below occurs twice (nor statusCode / result / size, nor key / value / init inside
+ *    their objects); unknown names are ignored (spray-json's product formats read members by name).
+ *  - namespace (EntityPath.scala:141-178): a string of bytes 0x20-0x7E without '"' and '\'; split at '/', empty parts
+ *    dropped, at least one part left; each part matches EntityName.REGEX (EntityPath.scala:206) with \w =
+ *    [A-Za-z0-9_] and is at most 256 characters.
+ *  - name (EntityPath.scala:222-234): one such part.
+ *  - subject (Subject.scala:46-67 behind ArgNormalizer.apply): the same character class, no leading or trailing
+ *    blank, at least 5 characters.
+ *  - activationId: a string of 32 characters [0-9a-f], written without escapes.
+ *  - cause: absent, null, or such a string.
+ *  - start, end (WhiskActivation.scala:161-168): a literal -?(0|[1-9][0-9]{0,17}).
+ *  - duration: absent, null, or a literal of that form.
+ *  - response (ActivationResult.scala:30-32, 249): an object; statusCode a literal -?(0|[1-9][0-9]{0,8}); size
+ *    absent, null or of that form; result any value.
+ *  - logs (ActivationLogs.scala:35): an array of strings.
+ *  - version (SemVer.scala:52-101): a string matching SemVer.REGEX, each part of at most 9 digits, not "0.0.0".
+ *  - publish: true or false.
+ *  - annotations (Parameter.scala:240-268): an array of objects; each has exactly one `key`, an unescaped string of
+ *    bytes 0x20-0x7E with a non-blank character, exactly one `value` (any), and at most one `init`, a boolean.
+ *  - presence: namespace, name, subject, activationId, start, end, response, logs, version, publish and annotations
+ *    are all present (spray-json applies no case-class defaults). */
+int owgs_process_result_acks(owgs_ctx* ctx, int32_t n, const char* bytes, const int64_t* off,
+                             const owgs_ack_out* out, int64_t now_ms, int32_t apply, int32_t out_summary[3]);
 
 /* ---- ActivationMessage serialisation + per-invoker topic fan-out ----
  * Replaces: ActivationMessage.serialize (jsonFormat11 + spray-json compactPrint, Message.scala:51-70, 170-175) and

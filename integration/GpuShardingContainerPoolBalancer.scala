@@ -38,6 +38,8 @@ import org.apache.openwhisk.core.loadBalancer.InvokerState.{Healthy, Offline, Un
 import org.apache.openwhisk.core.{ConfigKeys, WhiskConfig}
 import org.apache.openwhisk.spi.SpiLoader
 
+import spray.json._
+
 import scala.collection.mutable
 import scala.concurrent.{Future, Promise}
 
@@ -94,7 +96,59 @@ object OwgsNative {
                                             n: Int, outKind: Array[Byte], outTicket: Array[Int],
                                             outFlags: Array[Byte], nowMs: Long, apply: Int,
                                             outSummary: Array[Int]): Int
+  /** owgs_process_result_acks: one ack feed batch of all three message types (Message.scala:240-258).  Combined
+   *  messages complete like CompletionMessages, ResultMessages (outKind 7) are looked up only; outFlags bit3 = the
+   *  message carries a result, bit4 = it is a WhiskActivation object; outAid = 2 n words (hi, lo); outRespOff /
+   *  outRespLen = the span of the `response` value in bytes.  outSummary null: nothing is fed, nowMs = apply = 0. */
+  @native def processResultAcks(ctx: Long, bytes: Array[Byte], off: Array[Long], n: Int, outKind: Array[Byte],
+                                outInvoker: Array[Int], outTicket: Array[Int], outFlags: Array[Byte],
+                                outAid: Array[Long], outRespOff: Array[Long], outRespLen: Array[Int], nowMs: Long,
+                                apply: Int, outSummary: Array[Int]): Int
   @native def lastError(ctx: Long): String
+}
+
+/** processResult (CLB:235-243) over the outputs of OwgsNative.processResultAcks.  The promises of blocking invokes are
+ *  held in an array by the ticket the shim hands to trackActivationsTimed / publishActivations, so the device's
+ *  outTicket finds them without an ActivationId -> Promise map (activationPromises, CLB:241); `late` is that map kept
+ *  only for the messages whose entry is gone (outTicket -1: the result arrives after the completion or the timeout),
+ *  filled when an entry is removed while its promise is still open.  Only the `response` span of an accepted message
+ *  is deserialised, and only when somebody waits for it. */
+final class TicketPromises(capacity: Int) {
+  private val byTicket = new java.util.concurrent.atomic.AtomicReferenceArray[Promise[Either[ActivationId, WhiskActivation]]](capacity)
+  private val late = new java.util.concurrent.ConcurrentHashMap[(Long, Long), Promise[Either[ActivationId, WhiskActivation]]]()
+
+  def put(ticket: Int, p: Promise[Either[ActivationId, WhiskActivation]]): Unit = byTicket.set(ticket, p)
+
+  /** The entry of `ticket` was removed (RELEASED, or the expiry sweep): an open promise moves to the fallback map. */
+  def removed(ticket: Int, aidHi: Long, aidLo: Long): Unit = {
+    val p = byTicket.getAndSet(ticket, null)
+    if (p != null && !p.isCompleted) late.put((aidHi, aidLo), p)
+  }
+
+  /** One batch: kind / ticket / flags / aid / respOff / respLen as processResultAcks wrote them. */
+  def processResults(bytes: Array[Byte], n: Int, kind: Array[Byte], ticket: Array[Int], flags: Array[Byte],
+                     aid: Array[Long], respOff: Array[Long], respLen: Array[Int]): Unit = {
+    var i = 0
+    while (i < n) {
+      if ((flags(i) & 8) != 0) { // OWGS_ACKF_RESULT: an accepted Combined or Result message
+        val p =
+          if (ticket(i) >= 0) byTicket.get(ticket(i))
+          else late.remove((aid(2 * i), aid(2 * i + 1)))
+        if (p != null && !p.isCompleted) {
+          val text = new String(bytes, respOff(i).toInt, respLen(i), java.nio.charset.StandardCharsets.UTF_8)
+          val response: Either[ActivationId, WhiskActivation] =
+            if ((flags(i) & 16) != 0) Right(text.parseJson.convertTo[WhiskActivation]) // OWGS_ACKF_RIGHT
+            else Left(text.parseJson.convertTo[ActivationId])
+          p.trySuccess(response)
+        }
+        // a Combined message whose entry was found also completed it (outKind 3): the ticket is free again
+        if (kind(i) == 3 && ticket(i) >= 0) byTicket.set(ticket(i), null)
+      } else if (kind(i) == 3 && ticket(i) >= 0) {
+        removed(ticket(i), aid(2 * i), aid(2 * i + 1)) // a CompletionMessage: its ResultMessage may still come
+      }
+      i += 1
+    }
+  }
 }
 
 /** The direct buffers of one publishActivations call (owgs_jni.c reads the same layout):

@@ -462,6 +462,54 @@ JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00
     return rc;
 }
 
+/* processAcknowledgement for all three message types (owgs_process_result_acks): Combined messages complete like
+ * CompletionMessages, ResultMessages are looked up only.  outSummary null: nothing is fed (nowMs and apply must be 0);
+ * otherwise as processAcksSupervised.  outAid holds 2n words (hi, lo). */
+JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_processResultAcks(
+    JNIEnv* env, jobject self, jlong h, jbyteArray bytes, jlongArray off, jint n, jbyteArray outKind,
+    jintArray outInvoker, jintArray outTicket, jbyteArray outFlags, jlongArray outAid, jlongArray outRespOff,
+    jintArray outRespLen, jlong nowMs, jint apply, jintArray outSummary) {
+    if (!bytes || !off || !outKind || !outInvoker || !outTicket || !outFlags || !outAid || !outRespOff ||
+        !outRespLen || !n_fits(env, n, outKind, outInvoker, outTicket, outFlags) ||
+        !n_fits(env, n, outRespOff, outRespLen, NULL, NULL) || !n_fits(env, 2 * (jlong)n, outAid, NULL, NULL, NULL) ||
+        !n_fits(env, (jlong)n + 1, off, NULL, NULL, NULL) ||
+        (outSummary && !n_fits(env, 3, outSummary, NULL, NULL, NULL)))
+        return OWGS_EINVAL;
+    int64_t* po = jcopy_in(env, off, (jlong)n + 1, 8, 'J');
+    if (!po) return OWGS_ENOMEM;
+    const jlong nb = (*env)->GetArrayLength(env, bytes);
+    if (!offsets_fit(po, n, nb)) {
+        free(po);
+        return OWGS_EINVAL;
+    }
+    const size_t m = (size_t)(n > 0 ? n : 1);
+    char* pb = jcopy_in(env, bytes, nb, 1, 'B');
+    owgs_ack_out o;
+    o.kind = calloc(m, 1);
+    o.invoker = calloc(m, 4);
+    o.ticket = calloc(m, 4);
+    o.flags = calloc(m, 1);
+    o.aid = calloc(2 * m, 8);
+    o.resp_off = calloc(m, 8);
+    o.resp_len = calloc(m, 4);
+    int32_t summary[3] = {0, 0, 0};
+    int rc = OWGS_ENOMEM;
+    if (pb && o.kind && o.invoker && o.ticket && o.flags && o.aid && o.resp_off && o.resp_len)
+        rc = owgs_process_result_acks(CTX(h), n, pb, po, &o, nowMs, apply, outSummary ? summary : NULL);
+    if (rc == OWGS_OK) {
+        jcopy_out(env, outKind, n, o.kind, 'B');
+        jcopy_out(env, outInvoker, n, o.invoker, 'I');
+        jcopy_out(env, outTicket, n, o.ticket, 'I');
+        jcopy_out(env, outFlags, n, o.flags, 'B');
+        jcopy_out(env, outAid, 2 * (jlong)n, o.aid, 'J');
+        jcopy_out(env, outRespOff, n, o.resp_off, 'J');
+        jcopy_out(env, outRespLen, n, o.resp_len, 'I');
+        if (outSummary) jcopy_out(env, outSummary, 3, summary, 'I');
+    }
+    FREE_ALL(po, pb, o.kind, o.invoker, o.ticket, o.flags, o.aid, o.resp_off, o.resp_len);
+    return rc;
+}
+
 /* completeActivations (timeouts the shim keeps itself, OWGS_ACK_JVM messages), then the results to the FSM */
 JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_completeActivationsSupervised(
     JNIEnv* env, jobject self, jlong h, jbyteArray aid32, jintArray invokers, jbyteArray flags, jint n,

@@ -21,6 +21,8 @@ NONE, THROW_INDEX = -1, -2
 FLAG_OVERLOAD = 1
 REL_NOSUCHELEMENT, REL_OVERFLOW, REL_NOENTRY = 1, 2, 4
 ACK_FAIL, ACK_JVM, ACK_UNSUPPORTED, ACK_RELEASED, ACK_HEALTH, ACK_NOENTRY, ACK_FORCED_NOENTRY = range(7)
+ACK_RESULT = 7  # owgs_process_result_acks: an accepted ResultMessage
+ACKF_RESULT, ACKF_RIGHT = 8, 16  # ... and its out_flags bits: carries a result; the result is an object
 HEALTHY, UNHEALTHY, UNRESPONSIVE, OFFLINE = 0, 1, 2, 3
 EV_PING, EV_SUCCESS, EV_SYSTEM_ERROR, EV_TIMEOUT, EV_STATE_TIMEOUT = range(5)
 PING_FAIL, PING_UNSUPPORTED, PING_FED, PING_RANGE = 0, 2, 3, 4  # owgs_process_pings outcomes
@@ -69,6 +71,11 @@ class owgs_publish_io(C.Structure):
                 ("aid", C.c_void_p), ("ns", C.c_void_p), ("ticket", C.c_void_p), ("time_limit_ms", C.c_void_p),
                 ("now_ms", C.c_int64), ("out_invoker", C.c_void_p), ("out_flags", C.c_void_p),
                 ("out_ticket", C.c_void_p), ("out_existed", C.c_void_p)]
+
+
+class owgs_ack_out(C.Structure):
+    """include/owgs.h: owgs_ack_out (the seven output arrays of owgs_process_result_acks)."""
+    _fields_ = [(k, C.c_void_p) for k in ("kind", "invoker", "ticket", "flags", "aid", "resp_off", "resp_len")]
 
 
 class owgs_msg_out(C.Structure):
@@ -129,6 +136,7 @@ def lib() -> C.CDLL:
         "owgs_process_pings": (C.c_int, [P, i32, P, P, P, C.c_int64, i32, P, P, P, P]),
         "owgs_process_acks_supervised": (C.c_int, [P, i32, P, P, P, P, P, P, C.c_int64, i32, P]),
         "owgs_complete_activations_supervised": (C.c_int, [P, i32, P, P, P, P, P, P, C.c_int64, i32, P]),
+        "owgs_process_result_acks": (C.c_int, [P, i32, P, P, P, C.c_int64, i32, P]),
         "owgs_register_actions": (C.c_int, [P, i32, P, P, P, P, P, P, P, P, P, P, P]),
         "owgs_publish_batch": (C.c_int, [P, i32, P, P, u64, P, P]),
         "owgs_release_batch": (C.c_int, [P, i32, P, P, P]),

@@ -448,6 +448,29 @@ class GpuShardingContainerPoolBalancer:
                                                        int(now_ms), int(apply), _p(summ)))
         return kind[:n], inv[:n], tk[:n], fl[:n], tuple(int(x) for x in summ)
 
+    def process_result_acks(self, msgs, now_ms=None, apply: int = 0):
+        """processAcknowledgement for raw ack messages of all three types (Message.scala:240-258): CompletionMessages as
+        in process_acks, CombinedCompletionAndResultMessages completed like them, ResultMessages looked up only.
+        now_ms = None feeds nothing, otherwise the RELEASED / HEALTH outcomes go to the health FSM as in
+        process_acks_supervised.  (kind, invoker, ticket, flags, aid u64[n, 2], resp_off, resp_len, summary | None);
+        the `response` value of message i with flags & ACKF_RESULT is b"".join(msgs)[resp_off[i]:][:resp_len[i]]."""
+        n = len(msgs)
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m) for m in msgs])
+        buf = np.frombuffer(b"".join(msgs) + b"\0", dtype=np.uint8)
+        m = max(n, 1)
+        kind, fl = np.zeros(m, dtype=np.uint8), np.zeros(m, dtype=np.uint8)
+        inv, tk, rlen = (np.zeros(m, dtype=np.int32) for _ in range(3))
+        aid = np.zeros((m, 2), dtype=np.uint64)
+        roff = np.zeros(m, dtype=np.int64)
+        out = _lib.owgs_ack_out(*(_p(a) for a in (kind, inv, tk, fl, aid, roff, rlen)))
+        summ = np.zeros(3, dtype=np.int32) if now_ms is not None else None
+        self._chk(self._L.owgs_process_result_acks(self._h, n, _p(buf), _p(off), C.byref(out),
+                                                   int(now_ms) if now_ms is not None else 0, int(apply),
+                                                   _p(summ) if summ is not None else None))
+        return (kind[:n], inv[:n], tk[:n], fl[:n], aid[:n], roff[:n], rlen[:n],
+                tuple(int(x) for x in summ) if summ is not None else None)
+
     def complete_activations_supervised(self, aids, invokers, now_ms: int, apply: int = 0, forced=None,
                                         system_error=None, health=None):
         """complete_activations, then the results to the health FSM at now_ms (forced: Timeout, CLB:266-267):

@@ -39,6 +39,20 @@ int main() {
     EXPECT(owgs_complete_activations_supervised(nullptr, 1, aid, inv, cfl, kind, ticket, flags, int64_t(1) << 60, 2, summary),
            OWGS_EINVAL);
 
+    // owgs_process_result_acks: no context, with and without a summary, a NULL out, a NULL member
+    uint64_t aid2[2];
+    int64_t roff[1];
+    int32_t rlen[1];
+    owgs_ack_out ao = {kind, inst, ticket, flags, aid2, roff, rlen};
+    EXPECT(owgs_process_result_acks(nullptr, 1, ping, off, &ao, 5, 0, summary), OWGS_EINVAL);
+    EXPECT(owgs_process_result_acks(nullptr, 1, ping, off, &ao, 0, 0, nullptr), OWGS_EINVAL);
+    EXPECT(owgs_process_result_acks(nullptr, 1, ping, off, &ao, 7, 2, nullptr), OWGS_EINVAL);
+    EXPECT(owgs_process_result_acks(nullptr, 1, ping, off, nullptr, -1, 3, summary), OWGS_EINVAL);
+    EXPECT(owgs_process_result_acks(nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr), OWGS_EINVAL);
+    EXPECT(owgs_process_result_acks(nullptr, -1, ping, off, &ao, 0, 0, nullptr), OWGS_EINVAL);
+    ao.aid = nullptr;
+    EXPECT(owgs_process_result_acks(nullptr, 1, ping, off, &ao, 0, 0, nullptr), OWGS_EINVAL);
+
     // owgs_publish_activations: no context, no io, no summary
     const int32_t act[1] = {0};
     const uint64_t words[2] = {1, 2};

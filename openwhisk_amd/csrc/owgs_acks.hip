@@ -14,6 +14,10 @@
 //                            ActivationId.parse (32 chars [0-9a-f] -> 128-bit key), InvokerInstanceId.instance
 //                            (BigDecimal.intValue), userMemory (ByteSize regex + toLong), uniqueName/displayedName
 //                            (Option[String]), isSystemError (Option[Boolean]), transid == invokerHealth.
+//                            A template over RESULTS: <false> leaves a message with a `response` member to the JVM;
+//                            <true> (owgs_process_result_acks) also takes CombinedCompletionAndResultMessage and
+//                            ResultMessage: a `response` that is an id, or a WhiskActivation inside the accepted
+//                            subset of include/owgs.h, checked by inlined functions over the byte window.
 //   owgs_act_*_kernel        activationSlots as an open-addressing table in HBM: key = 128-bit activation id,
 //                            value = {action handle, caller ticket} plus the entry's namespace, completion-ack
 //                            deadline, invoker and arm sequence (owgs_expire.hip sweeps the deadlines, summarised per
@@ -92,9 +96,34 @@ __device__ __forceinline__ int unit_at(Win& W, int64_t& i) {
 #define K_DISPLAYED 7
 #define K_USERMEM 8
 #define K_NAME 9
-__constant__ char k_names[10][16] = {"activationId", "invoker", "isSystemError", "response", "transid",
-                                     "instance",     "uniqueName", "displayedName", "userMemory", "name"};
-__constant__ int k_len[10] = {12, 7, 13, 8, 7, 8, 10, 13, 10, 4};
+// the members of a `response` object (WhiskActivation, jsonFormat13), in the case class's order ...
+#define K_WA_NAMESPACE 10
+#define K_WA_NAME 11
+#define K_WA_SUBJECT 12
+#define K_WA_AID 13
+#define K_WA_START 14
+#define K_WA_END 15
+#define K_WA_CAUSE 16
+#define K_WA_RESPONSE 17
+#define K_WA_LOGS 18
+#define K_WA_VERSION 19
+#define K_WA_PUBLISH 20
+#define K_WA_ANNOTATIONS 21
+#define K_WA_DURATION 22
+// ... of its ActivationResponse (jsonFormat3) and of one annotation (Parameters.serdes)
+#define K_AR_STATUS 23
+#define K_AR_RESULT 24
+#define K_AR_SIZE 25
+#define K_P_KEY 26
+#define K_P_VALUE 27
+#define K_P_INIT 28
+__constant__ char k_names[29][16] = {"activationId", "invoker",    "isSystemError", "response",   "transid",
+                                     "instance",     "uniqueName", "displayedName", "userMemory", "name",
+                                     "namespace",    "name",       "subject",       "activationId", "start",
+                                     "end",          "cause",      "response",      "logs",       "version",
+                                     "publish",      "annotations", "duration",     "statusCode", "result",
+                                     "size",         "key",        "value",         "init"};
+__constant__ int k_len[29] = {12, 7, 13, 8, 7, 8, 10, 13, 10, 4, 9, 4, 7, 12, 5, 3, 5, 8, 4, 7, 7, 11, 8, 10, 6, 4, 3, 5, 4};
 
 // bitmask of the candidate names (lo..hi) the decoded key equals
 __device__ __forceinline__ int key_match(Win& W, int64_t k, int lo, int hi) {
@@ -392,12 +421,282 @@ __device__ __forceinline__ void instance_id(Win& W, int64_t a, int& inst, long l
     }
 }
 
-__global__ __launch_bounds__(256) void owgs_ack_parse_kernel(OwgsAckParseArgs A) {
+// ActivationId.serdes.read on the validated JSON string at a (ActivationId.scala:58-95): 32 decoded units of [0-9a-f]
+// -> the 128-bit key.  A wrong length or another ASCII unit is a deserializationError (fail); a non-ASCII unit may be a
+// digit of Char.isDigit (ActivationId.scala:50) and is left to the JVM (unsup).  Both the CompletionMessage's
+// `activationId` and a `response` that is a string (Left, Message.scala:231-233) go through here.
+__device__ __forceinline__ void activation_id(Win& W, int64_t a, u64& hi, u64& lo, bool& fail, bool& unsup) {
+    int64_t j = a + 1;
+    int len = 0;
+    bool bad = false, nonascii = false;
+    for (;;) {
+        const int u = unit_at(W, j);
+        if (u < 0) break;
+        nonascii |= u >= 0x80;
+        const int h = (u >= '0' && u <= '9') ? u - '0' : (u >= 'a' && u <= 'f') ? u - 'a' + 10 : -1;
+        if (h < 0) bad = true;
+        else if (len < 16) hi = (hi << 4) | (u64)h;
+        else if (len < 32) lo = (lo << 4) | (u64)h;
+        ++len;
+    }
+    if (nonascii) unsup = true;
+    else if (len != 32 || bad) fail = true;
+}
+
+// ------------------------------------------------------------------------------------------ accepted subset
+// A `response` object (Right(WhiskActivation), Message.scala:235) is taken on the device only inside the accepted
+// subset of include/owgs.h ("accepted subset of a response object"): a sufficient condition for
+// convertTo[WhiskActivation] to succeed, checked over the raw bytes of the already validated message.  Every function
+// returns false for anything outside its rule; the caller then reports OWGS_ACK_JVM, never FAIL.
+
+// the member name at k (its opening quote) among k_names[lo..hi], compared byte by byte; a name written with an escape
+// sets esc (and matches nothing)
+__device__ __forceinline__ int key_match_raw(Win& W, int64_t k, int lo, int hi, bool& esc) {
+    int64_t i = k + 1;
+    uint32_t alive = ((1u << (hi + 1)) - 1u) & ~((1u << lo) - 1u);
+    int n = 0;
+    for (;;) {
+        const int u = W.at(i);
+        if (u == '"') break;
+        if (u == '\\') {
+            esc = true;
+            return -1;
+        }
+        for (int c = lo; c <= hi; ++c)
+            if (((alive >> c) & 1u) && (n >= k_len[c] || u != k_names[c][n])) alive &= ~(1u << c);
+        ++n;
+        ++i;
+    }
+    for (int c = lo; c <= hi; ++c)
+        if (((alive >> c) & 1u) && n == k_len[c]) return c;
+    return -1;
+}
+
+// -?(0|[1-9][0-9]{0,maxd-1}) and nothing more: no fraction, no exponent (the grammar has excluded leading zeros)
+__device__ __forceinline__ bool int_literal(Win& W, int64_t a, int maxd) {
+    if (W.at(a) == '-') ++a;
+    int nd = 0, c;
+    while ((c = W.at(a)) >= '0' && c <= '9') ++a, ++nd;
+    return nd >= 1 && nd <= maxd && c != '.' && c != 'e' && c != 'E';
+}
+
+// a string of exactly 32 raw [0-9a-f] -> hi, lo
+__device__ __forceinline__ bool hex32(Win& W, int64_t a, u64& hi, u64& lo) {
+    if (W.at(a) != '"') return false;
+    u64 h = 0, l = 0;
+    bool ok = true;
+    for (int k = 0; k < 32; ++k) {
+        const int c = W.at(a + 1 + k);
+        const int x = (c >= '0' && c <= '9') ? c - '0' : (c >= 'a' && c <= 'f') ? c - 'a' + 10 : -1;
+        ok &= x >= 0;
+        if (!ok) break;  // (a closing quote stops the walk inside the string)
+        if (k < 16) h = (h << 4) | (u64)x;
+        else l = (l << 4) | (u64)x;
+    }
+    hi = h;
+    lo = l;
+    return ok && W.at(a + 33) == '"';
+}
+
+// EntityPath / EntityName (EntityPath.scala:141-162, 206, 222-224): printable ASCII without '"' and '\', split at '/'
+// (sep; EntityName has no separator: '/' is outside its class) with the empty parts dropped; every part matches
+// EntityName.REGEX -- first [A-Za-z0-9_], then [\w@ .&-], no trailing blank, at most 256 characters.  A path needs one
+// part or more, a name exactly one.
+__device__ __forceinline__ bool entity_parts(Win& W, int64_t a, bool sep) {
+    if (W.at(a) != '"') return false;
+    int parts = 0, len = 0, last = 0;
+    bool ok = true;
+    for (int64_t i = a + 1;; ++i) {
+        const int c = W.at(i);
+        if (c == '"' || (sep && c == '/')) {
+            if (len > 0) {
+                ok &= last != ' ' && len <= 256;
+                ++parts;
+                len = 0;
+            }
+            if (c == '"') break;
+            continue;
+        }
+        const bool w = (c >= '0' && c <= '9') || (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z') || c == '_';
+        const bool mid = w || c == '@' || c == ' ' || c == '.' || c == '&' || c == '-';
+        if (len == 0 ? !w : !mid) return false;  // also '\', bytes >= 0x80 and the end of the window (-1)
+        last = c;
+        ++len;
+    }
+    return ok && (sep ? parts >= 1 : parts == 1);
+}
+
+// a string of printable ASCII (0x20-0x7E) without '"' and '\'; *n its length, *first / *last its end characters,
+// *nonblank whether a character other than ' ' occurs
+__device__ __forceinline__ bool plain_string(Win& W, int64_t a, int* n, int* first, int* last, bool* nonblank) {
+    if (W.at(a) != '"') return false;
+    int len = 0, f = 0, l = 0;
+    bool nb = false;
+    for (int64_t i = a + 1;; ++i) {
+        const int c = W.at(i);
+        if (c == '"') break;
+        if (c < 0x20 || c > 0x7E || c == '\\') return false;
+        if (len == 0) f = c;
+        l = c;
+        nb |= c != ' ';
+        ++len;
+    }
+    *n = len, *first = f, *last = l, *nonblank = nb;
+    return true;
+}
+
+// SemVer (SemVer.scala:52-101): "major.minor.patch", each (0|[1-9][0-9]{0,8}) so that toInt succeeds, not 0.0.0
+__device__ __forceinline__ bool semver(Win& W, int64_t a) {
+    if (W.at(a) != '"') return false;
+    int64_t i = a + 1;
+    bool nonzero = false;
+    for (int part = 0; part < 3; ++part) {
+        int nd = 0, c, c0 = W.at(i);
+        while ((c = W.at(i)) >= '0' && c <= '9') ++i, ++nd;
+        if (nd < 1 || nd > 9 || (c0 == '0' && nd > 1)) return false;
+        nonzero |= c0 != '0';
+        if (c != (part < 2 ? '.' : '"')) return false;
+        ++i;
+    }
+    return nonzero;
+}
+
+// The checks of container values walk them once and return the index after the value (-1: outside the rule), so that
+// the caller does not scan the value again to get past it.
+
+// ActivationLogs (ActivationLogs.scala:35): an array whose elements are all strings
+__device__ __forceinline__ int64_t string_array(Win& W, int64_t a) {
+    if (W.at(a) != '[') return -1;
+    int64_t j = a + 1;
+    while (is_ws(W.at(j))) ++j;
+    if (W.at(j) == ']') return j + 1;
+    for (;;) {
+        while (is_ws(W.at(j))) ++j;
+        if (W.at(j) != '"') return -1;
+        j = scan_string(W, j);
+        while (is_ws(W.at(j))) ++j;
+        if (W.at(j) != ',') return j + 1;  // ']'
+        ++j;
+    }
+}
+
+// the members of the validated object at a, one call of f(id, value index) per member whose raw name is
+// k_names[lo..hi] (id) or another name (-1).  f returns -1 (outside the rule), 0 (the value is fine or of no interest
+// and has not been walked) or the index after the value.  Returns the index after the object, or -1 as soon as a name
+// is escaped, one of lo..hi occurs twice or f returns -1.  seen = the names met (bit id - lo).
+template <class F>
+__device__ __forceinline__ int64_t object_members(Win& W, int64_t a, int lo, int hi, uint32_t& seen, F f) {
+    seen = 0;
+    int64_t j = a + 1;
+    while (is_ws(W.at(j))) ++j;
+    if (W.at(j) == '}') return j + 1;
+    for (;;) {
+        while (is_ws(W.at(j))) ++j;
+        const int64_t k = j;
+        j = scan_string(W, j);
+        while (is_ws(W.at(j))) ++j;
+        ++j;  // ':'
+        while (is_ws(W.at(j))) ++j;
+        bool esc = false;
+        const int id = key_match_raw(W, k, lo, hi, esc);
+        if (esc) return -1;
+        if (id >= 0) {
+            const uint32_t bit = 1u << (id - lo);
+            if (seen & bit) return -1;
+            seen |= bit;
+        }
+        const int64_t r = f(id, j);
+        if (r < 0) return -1;
+        j = r > 0 ? r : skip_value(W, j);
+        while (is_ws(W.at(j))) ++j;
+        if (W.at(j) != ',') return j + 1;  // '}'
+        ++j;
+    }
+}
+
+// ActivationResponse (jsonFormat3, ActivationResult.scala:30-32, 249): statusCode an Int literal, size absent, null or
+// one, result anything
+__device__ __forceinline__ int64_t activation_response(Win& W, int64_t a) {
+    if (W.at(a) != '{') return -1;
+    uint32_t seen;
+    const int64_t end = object_members(W, a, K_AR_STATUS, K_AR_SIZE, seen, [&](int id, int64_t j) -> int64_t {
+        if (id == K_AR_STATUS) return int_literal(W, j, 9) ? 0 : -1;
+        if (id == K_AR_SIZE) return (W.at(j) == 'n' || int_literal(W, j, 9)) ? 0 : -1;
+        return 0;
+    });
+    return (seen & 1u) ? end : -1;
+}
+
+// Parameters.serdes.read (Parameter.scala:240-268): an array of objects, each with one "key" (a plain string with a
+// non-blank character), one "value" and at most one "init", a boolean
+__device__ __forceinline__ int64_t annotations(Win& W, int64_t a) {
+    if (W.at(a) != '[') return -1;
+    int64_t j = a + 1;
+    while (is_ws(W.at(j))) ++j;
+    if (W.at(j) == ']') return j + 1;
+    for (;;) {
+        while (is_ws(W.at(j))) ++j;
+        if (W.at(j) != '{') return -1;
+        uint32_t seen;
+        j = object_members(W, j, K_P_KEY, K_P_INIT, seen, [&](int id, int64_t q) -> int64_t {
+            if (id == K_P_KEY) {
+                int n, f, l;
+                bool nb;
+                return (plain_string(W, q, &n, &f, &l, &nb) && nb) ? 0 : -1;
+            }
+            if (id == K_P_INIT) return (W.at(q) == 't' || W.at(q) == 'f') ? 0 : -1;
+            return 0;
+        });
+        if (j < 0 || (seen & 3u) != 3u) return -1;
+        while (is_ws(W.at(j))) ++j;
+        if (W.at(j) != ',') return j + 1;  // ']'
+        ++j;
+    }
+}
+
+// WhiskActivation (jsonFormat13, WhiskActivation.scala:52-64, 182) inside the accepted subset: the index after the
+// object (-1: outside the subset); hi / lo = its activationId
+__device__ __forceinline__ int64_t whisk_activation(Win& W, int64_t a, u64& hi, u64& lo) {
+    uint32_t seen;
+    const int64_t end = object_members(W, a, K_WA_NAMESPACE, K_WA_DURATION, seen, [&](int id, int64_t j) -> int64_t {
+        bool ok = true;
+        if (id == K_WA_NAMESPACE) ok = entity_parts(W, j, true);
+        else if (id == K_WA_NAME) ok = entity_parts(W, j, false);
+        else if (id == K_WA_SUBJECT) {  // Subject.scala:46-67 behind ArgNormalizer.apply: trim is the identity
+            int n, f, l;
+            bool nb;
+            ok = plain_string(W, j, &n, &f, &l, &nb) && n >= 5 && f != ' ' && l != ' ';
+        } else if (id == K_WA_AID) ok = hex32(W, j, hi, lo);
+        else if (id == K_WA_CAUSE) {
+            u64 ch, cl;
+            ok = W.at(j) == 'n' || hex32(W, j, ch, cl);
+        } else if (id == K_WA_START || id == K_WA_END) ok = int_literal(W, j, 18);  // WhiskActivation.scala:161-168
+        else if (id == K_WA_DURATION) ok = W.at(j) == 'n' || int_literal(W, j, 18);
+        else if (id == K_WA_RESPONSE) return activation_response(W, j);
+        else if (id == K_WA_LOGS) return string_array(W, j);
+        else if (id == K_WA_VERSION) ok = semver(W, j);
+        else if (id == K_WA_PUBLISH) ok = W.at(j) == 't' || W.at(j) == 'f';
+        else if (id == K_WA_ANNOTATIONS) return annotations(W, j);
+        return ok ? 0 : -1;
+    });
+    const uint32_t need = 0x1FFFu & ~(1u << (K_WA_CAUSE - K_WA_NAMESPACE)) & ~(1u << (K_WA_DURATION - K_WA_NAMESPACE));
+    return (seen & need) == need ? end : -1;
+}
+
+template <bool RESULTS> struct OwgsAckParseSel { typedef OwgsAckParseArgs type; };
+template <> struct OwgsAckParseSel<true> { typedef OwgsAckParseResultArgs type; };
+
+// RESULTS = false: the parser of owgs_process_acks* (a `response` member: OWGS_ACK_JVM).  RESULTS = true:
+// owgs_process_result_acks, which classifies those messages too (include/owgs.h).
+template <bool RESULTS>
+__global__ __launch_bounds__(256) void owgs_ack_parse_kernel(typename OwgsAckParseSel<RESULTS>::type A) {
     const int m = blockIdx.x * 256 + threadIdx.x;
     if (m >= A.n) return;
     const int64_t b = A.off[m], e = A.off[m + 1];
     Win W(A.bytes, b, e);
     int kind = OWGS_ACK_FAIL, inst = -1, sys = 0, health = 0;
+    int result = 0, right = 0;  // RESULTS: the message has a `response` member; it is an object
+    int64_t resp = 0, resp_end = 0;
     u64 hi = 0, lo = 0;
     if (has_ffff(W, b, e)) {
         kind = OWGS_ACK_UNSUPPORTED;
@@ -408,46 +707,47 @@ __global__ __launch_bounds__(256) void owgs_ack_parse_kernel(OwgsAckParseArgs A)
         const int ev = scan_message<K_AID, K_TID>(W, b, e, v, top_obj);
         if (ev == EV_UNSUP) kind = OWGS_ACK_UNSUPPORTED;
         else if (ev == EV_ERR || !top_obj) kind = OWGS_ACK_FAIL;
-        else if (v[K_RESP] >= 0) kind = OWGS_ACK_JVM;
-        else if (v[K_INV] < 0) kind = OWGS_ACK_FAIL;
+        else if (!RESULTS && v[K_RESP] >= 0) kind = OWGS_ACK_JVM;
+        else if (v[K_INV] < 0 && (!RESULTS || v[K_RESP] < 0)) kind = OWGS_ACK_FAIL;
         else {
-            // ------------------------------------------------------------ phase 2: CompletionMessage members
-            bool fail = v[K_TID] < 0 || v[K_AID] < 0, unsup = false;
-            if (v[K_AID] >= 0) {
+            // ------------------------------------------------------------ phase 2: the members of the message type
+            // CompletionMessage (jsonFormat4, Message.scala:208-209); with RESULTS and a `response` member a
+            // CombinedCompletionAndResultMessage (jsonFormat4, Message.scala:191-193: `invoker` present) or a
+            // ResultMessage (jsonFormat2, Message.scala:221), whose id is the response's
+            const bool has_resp = RESULTS && v[K_RESP] >= 0, has_inv = !RESULTS || v[K_INV] >= 0;
+            bool fail = v[K_TID] < 0, unsup = false, jvm = false;
+            if (has_resp) {
+                const int c = W.at(v[K_RESP]);
+                if (c == '"') {  // Left (Message.scala:231-233)
+                    activation_id(W, v[K_RESP], hi, lo, fail, unsup);
+                    resp_end = scan_string(W, v[K_RESP]);
+                } else if (c == '{') {  // Right (Message.scala:235); the check's walk gives the value's end
+                    right = 1;
+                    resp_end = whisk_activation(W, v[K_RESP], hi, lo);
+                    jvm = resp_end < 0;
+                } else {
+                    fail = true;  // Message.scala:236
+                }
+                result = 1;
+            } else if (v[K_AID] >= 0) {
                 const int64_t a = v[K_AID];
                 const int c = W.at(a);
-                if (c == '"') {
-                    int64_t j = a + 1;
-                    int len = 0;
-                    bool bad = false, nonascii = false;
-                    for (;;) {
-                        const int u = unit_at(W, j);
-                        if (u < 0) break;
-                        nonascii |= u >= 0x80;
-                        const int h = (u >= '0' && u <= '9') ? u - '0' : (u >= 'a' && u <= 'f') ? u - 'a' + 10 : -1;
-                        if (h < 0) bad = true;
-                        else if (len < 16) hi = (hi << 4) | (u64)h;
-                        else if (len < 32) lo = (lo << 4) | (u64)h;
-                        ++len;
-                    }
-                    if (nonascii) unsup = true;
-                    else if (len != 32 || bad) fail = true;
-                } else if (num_start(c)) {
-                    unsup = true;
-                } else {
-                    fail = true;
-                }
+                if (c == '"') activation_id(W, a, hi, lo, fail, unsup);
+                else if (num_start(c)) unsup = true;
+                else fail = true;
+            } else {
+                fail = true;
             }
-            if (v[K_SYS] >= 0) {
+            if (has_inv && v[K_SYS] >= 0) {
                 const int c = W.at(v[K_SYS]);
                 if (c == 't') sys = 1;
                 else if (c != 'f' && c != 'n') fail = true;
             }
-            {
+            if (has_inv) {
                 long long mem;
                 instance_id(W, v[K_INV], inst, mem, fail, unsup);
             }
-            if (v[K_TID] >= 0 && W.at(v[K_TID]) == '[') {
+            if (has_inv && v[K_TID] >= 0 && W.at(v[K_TID]) == '[') {
                 int64_t el[3] = {-1, -1, -1};
                 int ne = 0;
                 int64_t j = v[K_TID] + 1;
@@ -486,13 +786,26 @@ __global__ __launch_bounds__(256) void owgs_ack_parse_kernel(OwgsAckParseArgs A)
                     }
                 }
             }
-            kind = fail ? OWGS_ACK_FAIL : unsup ? OWGS_ACK_UNSUPPORTED : OWGS_ACK_COMPLETION;
+            // an object outside the subset stays the JVM's whatever else the message holds; then FAIL before UNSUPPORTED
+            kind = jvm ? OWGS_ACK_JVM
+                       : fail ? OWGS_ACK_FAIL
+                              : unsup ? OWGS_ACK_UNSUPPORTED : has_inv ? OWGS_ACK_COMPLETION : OWGS_ACK_RESULT_MSG;
+            if (RESULTS) resp = v[K_RESP];
         }
     }
     if (kind != OWGS_ACK_COMPLETION) sys = health = 0;  // only a parsed CompletionMessage carries them
     A.key[m] = make_ulonglong2(hi, lo);
     A.inst[m] = inst;
-    A.info[m] = (uint8_t)(kind | (sys << 4) | (health << 5) | (A.forced ? (A.forced[m] & 1) << 6 : 0));
+    if constexpr (RESULTS) {
+        // an accepted message with a result: the span of its `response` value in the caller's bytes[], and the two
+        // free bits of the record (3: carries a result, 7: the result is an object)
+        const bool acc = result && (kind == OWGS_ACK_COMPLETION || kind == OWGS_ACK_RESULT_MSG);
+        A.resp_off[m] = acc ? resp + A.off_base : 0;
+        A.resp_len[m] = acc ? (int32_t)(resp_end - resp) : 0;
+        A.info[m] = (uint8_t)(kind | (sys << 4) | (health << 5) | (acc ? 8 | (right << 7) : 0));
+    } else {
+        A.info[m] = (uint8_t)(kind | (sys << 4) | (health << 5) | (A.forced ? (A.forced[m] & 1) << 6 : 0));
+    }
 }
 
 // PingMessage.parse (Message.scala:261-268: jsonFormat(PingMessage.apply _, "name")) for the raw messages of the
@@ -732,13 +1045,28 @@ __global__ __launch_bounds__(256) void owgs_act_publish_kernel(OwgsActTable T, i
     T.owner[s] = 0x7FFFFFFF;
 }
 
-// completion step 1: find each message's entry; the lowest message index of an entry removes it
+// completion step 1: find each message's entry; the lowest message index of an entry removes it.  results != 0: a
+// result-only record (OWGS_ACK_RESULT_MSG) finds its entry too, without a claim on it: it removes nothing
 __global__ __launch_bounds__(256) void owgs_act_find_kernel(OwgsActTable T, const ulonglong2* key, int32_t n,
-                                                            const uint8_t* info, int32_t* slot) {
+                                                            const uint8_t* info, int32_t* slot, int32_t results) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     int r = -1;
-    if ((info[i] & 7) == OWGS_ACK_COMPLETION) {
+    const int kd = info[i] & 7;
+    if (results && kd == OWGS_ACK_RESULT_MSG) {
+        const ulonglong2 k = key[i];
+        const u64 mask = (u64)T.cap - 1;
+        u64 s = aid_hash(k) & mask;
+        for (u64 probes = 0; probes <= mask; ++probes) {
+            const u64 w = T.tw[s];
+            if (w == TW_EMPTY) break;
+            if (w == TW_READY && keq(T.tk[s], k)) {
+                r = (int)s;
+                break;
+            }
+            s = (s + 1) & mask;
+        }
+    } else if (kd == OWGS_ACK_COMPLETION) {
         const ulonglong2 k = key[i];
         const u64 mask = (u64)T.cap - 1;
         u64 s = aid_hash(k) & mask;
@@ -768,7 +1096,7 @@ __global__ __launch_bounds__(256) void owgs_ack_resolve_kernel(OwgsActTable T, i
                                                                int32_t* r_inv, int32_t* r_mem, int32_t* r_maxc,
                                                                int32_t* r_slot, uint8_t* out_kind,
                                                                int32_t* out_ticket, unsigned long long* counters,
-                                                               OwgsInflight F) {
+                                                               OwgsInflight F, int32_t results) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     int h = OWGS_NONE_V, mb = 0;
     bool bb = false;
@@ -776,7 +1104,12 @@ __global__ __launch_bounds__(256) void owgs_ack_resolve_kernel(OwgsActTable T, i
         const int k = info[i] & 7;
         const int s = slot[i];
         int outk = k, tk = -1, ri = 0x7FFFFFFF, rm = 1, rc = 1, rs = 0;
-        if (k == OWGS_ACK_COMPLETION) {
+        if (results && k == OWGS_ACK_RESULT_MSG) {
+            // processResult (CLB:235-243) looks the id up at the message's turn: the entry was there when the batch
+            // began and no message before this one removes it (owner = the lowest index that does, INT_MAX: none).
+            // Nothing is removed, released or counted: the lane enters the reductions below with the neutral values.
+            if (s >= 0 && T.owner[s] > i) tk = T.tv[s].y;
+        } else if (k == OWGS_ACK_COMPLETION) {
             if (s >= 0 && T.owner[s] == i) {
                 const int2 v = T.tv[s];
                 outk = OWGS_ACK_RELEASED;
@@ -817,13 +1150,23 @@ __global__ __launch_bounds__(256) void owgs_act_remove_kernel(OwgsActTable T, in
     T.owner[s] = 0x7FFFFFFF;
 }
 
-// out_flags = isSystemError | release flags << 1
+// out_flags = isSystemError | release flags << 1.  out_aid != null (owgs_process_result_acks): also the record's
+// result bits as OWGS_ACKF_RESULT / OWGS_ACKF_RIGHT, and the id of every accepted message (hi, lo), 0 for the others
 __global__ __launch_bounds__(256) void owgs_ack_flags_kernel(int32_t n, const uint8_t* info, const uint8_t* rflags,
-                                                             const uint8_t* out_kind, uint8_t* out_flags) {
+                                                             const uint8_t* out_kind, uint8_t* out_flags,
+                                                             const ulonglong2* key, unsigned long long* out_aid) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const bool rel = out_kind[i] == OWGS_ACK_RELEASED;
-    out_flags[i] = (uint8_t)(((info[i] >> 4) & 1) | (rel ? (rflags[i] & 3) << 1 : 0));
+    int f = ((info[i] >> 4) & 1) | (rel ? (rflags[i] & 3) << 1 : 0);
+    if (out_aid) {
+        f |= ((info[i] >> 3) & 1) << 3 | ((info[i] >> 7) & 1) << 4;
+        const bool acc = out_kind[i] >= OWGS_ACK_RELEASED;
+        const ulonglong2 k = key[i];
+        out_aid[2 * (size_t)i] = acc ? k.x : 0ull;
+        out_aid[2 * (size_t)i + 1] = acc ? k.y : 0ull;
+    }
+    out_flags[i] = (uint8_t)f;
 }
 
 // rehash live entries into a fresh table (all keys distinct: plain CAS insertion); the namespace, the deadline, the
@@ -864,7 +1207,13 @@ __global__ __launch_bounds__(256) void owgs_act_init_kernel(OwgsActTable T) {
 
 extern "C" hipError_t owgs_launch_ack_parse(const OwgsAckParseArgs* a, hipStream_t st) {
     if (a->n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(owgs_ack_parse_kernel, GRID(a->n), *a);
+    hipLaunchKernelGGL(owgs_ack_parse_kernel<false>, GRID(a->n), *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t owgs_launch_ack_parse_results(const OwgsAckParseResultArgs* a, hipStream_t st) {
+    if (a->n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(owgs_ack_parse_kernel<true>, GRID(a->n), *a);
     return hipGetLastError();
 }
 
@@ -908,17 +1257,18 @@ extern "C" hipError_t owgs_launch_act_track(const OwgsActTable* T, const ulonglo
 // find + resolve: afterwards r_* hold the release records for owgs_release_seq_kernel (message order)
 extern "C" hipError_t owgs_launch_ack_complete(const OwgsActTable* T, const OwgsAckCompleteArgs* a, hipStream_t st) {
     if (a->n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(owgs_act_find_kernel, GRID(a->n), *T, a->key, a->n, a->info, a->slot);
+    hipLaunchKernelGGL(owgs_act_find_kernel, GRID(a->n), *T, a->key, a->n, a->info, a->slot, a->results);
     hipLaunchKernelGGL(owgs_ack_resolve_kernel, GRID(a->n), *T, a->n, a->info, a->inst, a->slot, a->act_mem,
                        a->act_maxc, a->act_slot, a->n_slots, a->r_inv, a->r_mem, a->r_maxc, a->r_slot, a->out_kind,
-                       a->out_ticket, a->counters, a->fl);
+                       a->out_ticket, a->counters, a->fl, a->results);
     hipLaunchKernelGGL(owgs_act_remove_kernel, GRID(a->n), *T, a->n, a->slot);
     return hipGetLastError();
 }
 
 extern "C" hipError_t owgs_launch_ack_flags(int32_t n, const uint8_t* info, const uint8_t* rflags,
-                                            const uint8_t* out_kind, uint8_t* out_flags, hipStream_t st) {
+                                            const uint8_t* out_kind, uint8_t* out_flags, const ulonglong2* key,
+                                            unsigned long long* out_aid, hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(owgs_ack_flags_kernel, GRID(n), n, info, rflags, out_kind, out_flags);
+    hipLaunchKernelGGL(owgs_ack_flags_kernel, GRID(n), n, info, rflags, out_kind, out_flags, key, out_aid);
     return hipGetLastError();
 }

@@ -96,7 +96,9 @@ extern "C" hipError_t owgs_launch_rate_grow(const long long* old_min, const int3
                                             long long* new_min, int32_t* new_cnt, int32_t new_cap, hipStream_t st);
 extern "C" hipError_t owgs_launch_ack_complete(const OwgsActTable* T, const OwgsAckCompleteArgs* a, hipStream_t st);
 extern "C" hipError_t owgs_launch_ack_flags(int32_t n, const uint8_t* info, const uint8_t* rflags,
-                                            const uint8_t* out_kind, uint8_t* out_flags, hipStream_t st);
+                                            const uint8_t* out_kind, uint8_t* out_flags, const ulonglong2* key,
+                                            unsigned long long* out_aid, hipStream_t st);
+extern "C" hipError_t owgs_launch_ack_parse_results(const OwgsAckParseResultArgs* a, hipStream_t st);
 extern "C" hipError_t owgs_launch_health_init(uint8_t* s, uint32_t* ring, int64_t* last, int64_t* tick, int64_t* mem,
                                               int32_t* tests, int32_t from, int32_t to, hipStream_t st);
 extern "C" size_t owgs_health_sort_bytes(int32_t n, int32_t bits);
@@ -365,6 +367,10 @@ struct owgs_ctx {
     DevBuf<int32_t> p_minv;
     void* p_pin = nullptr;
     size_t p_pin_bytes = 0;
+    // owgs_process_result_acks: its seven output arrays as one device block, and the pinned block they come back in
+    DevBuf<uint8_t> r_blk;
+    void* r_pin = nullptr;
+    size_t r_pin_bytes = 0;
     // invoker health supervision (owgs_health.hip): persistent SoA by invoker id + per-batch scratch
     DevBuf<uint8_t> h_st, he_kind, he_temp;
     DevBuf<uint32_t> h_ring;
@@ -1950,6 +1956,9 @@ void owgs_destroy(owgs_ctx* c) {
     c->p_minv.release();
     if (c->p_pin) (void)hipHostFree(c->p_pin);
     c->p_pin = nullptr;
+    c->r_blk.release();
+    if (c->r_pin) (void)hipHostFree(c->r_pin);
+    c->r_pin = nullptr;
     DevBuf<char>* mc[] = {&c->m_ta, &c->m_tb, &c->m_rci, &c->m_tid, &c->m_content, &c->m_trace, &c->m_out};
     for (auto* b : mc) b->release();
     DevBuf<int64_t>* m64[] = {&c->m_ta_off, &c->m_tb_off, &c->m_tid_off, &c->m_tid_start, &c->m_content_off,
@@ -3896,9 +3905,18 @@ static void inflight_release(owgs_ctx* c, const unsigned long long* cnt) {
     c->f_mb_blackbox -= (long long)cnt[OWGS_CNT_BLACKBOX_MB];
 }
 
+// owgs_process_result_acks' share of the tail: result-only records look their entry up, the flags kernel adds the result
+// bits and the ids, and the output block's copy is queued before the tail's one synchronisation
+struct AckResultTail {
+    unsigned long long* d_aid;  // [2n] in the block
+    void* pin;                  // pinned destination
+    const void* blk;            // the block
+    size_t bytes;
+};
+
 // shared tail: info/key/inst of n messages are in k_info/k_key/k_inst; resolve, release in order, flags
 static int ack_complete(owgs_ctx* c, int32_t n, uint8_t* d_kind, int32_t* d_ticket, uint8_t* d_flags,
-                        hipStream_t st) {
+                        hipStream_t st, const AckResultTail* rt = nullptr) {
     if (c->t_cap == 0) {
         int rc = act_reserve(c, 0);
         if (rc) return rc;
@@ -3936,6 +3954,7 @@ static int ack_complete(owgs_ctx* c, int32_t n, uint8_t* d_kind, int32_t* d_tick
     a.out_ticket = d_ticket;
     a.counters = c->k_cnt.p;
     a.fl = inflight_args(c);
+    a.results = rt ? 1 : 0;
     HIPCHK(c, owgs_launch_ack_complete(&T, &a, st));
     if (c->large) {  // the large-state engine applies the records in message order (owgs_seq.hip)
         const int64_t offs[4] = {0, (int64_t)n, 0, 0};
@@ -3951,7 +3970,9 @@ static int ack_complete(owgs_ctx* c, int32_t n, uint8_t* d_kind, int32_t* d_tick
         S.rel_flags = c->d_rflags.p;
         int rs = seq_run(c, S, st);
         if (rs) return rs;
-        HIPCHK(c, owgs_launch_ack_flags(n, c->k_info.p, c->d_rflags.p, d_kind, d_flags, st));
+        HIPCHK(c, owgs_launch_ack_flags(n, c->k_info.p, c->d_rflags.p, d_kind, d_flags, c->k_key.p,
+                                        rt ? rt->d_aid : nullptr, st));
+        if (rt) HIPCHK(c, hipMemcpyAsync(rt->pin, rt->blk, rt->bytes, hipMemcpyDeviceToHost, st));
         unsigned long long cnt[OWGS_CNT_WORDS];
         HIPCHK(c, hipMemcpyAsync(cnt, c->k_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
@@ -3981,7 +4002,9 @@ static int ack_complete(owgs_ctx* c, int32_t n, uint8_t* d_kind, int32_t* d_tick
     R.ovf = ovf_args(c);
     R.w = watch_args(c);
     HIPCHK(c, owgs_launch_release_seq(&R, st));
-    HIPCHK(c, owgs_launch_ack_flags(n, c->k_info.p, c->d_rflags.p, d_kind, d_flags, st));
+    HIPCHK(c, owgs_launch_ack_flags(n, c->k_info.p, c->d_rflags.p, d_kind, d_flags, c->k_key.p,
+                                    rt ? rt->d_aid : nullptr, st));
+    if (rt) HIPCHK(c, hipMemcpyAsync(rt->pin, rt->blk, rt->bytes, hipMemcpyDeviceToHost, st));
     unsigned long long cnt[OWGS_CNT_WORDS];
     HIPCHK(c, hipMemcpyAsync(cnt, c->k_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -4718,6 +4741,93 @@ int owgs_complete_activations_supervised(owgs_ctx* c, int32_t n, const char* aid
     if (rc) return rc;
     return feed_acks(c, n, out_kind, invoker, c->k_kind.p, c->k_inst.p, c->k_oflags.p, c->k_info.p, now_ms, apply,
                      out_summary);
+}
+
+// ------------------------------------------------------------------------------------------ result-carrying acks
+// The seven outputs lie in one device block (64-bit arrays first, then the 32-bit ones, then the bytes) and come back
+// with one copy into pinned memory, queued behind the flags kernel and ahead of the tail's synchronisation.
+int owgs_process_result_acks(owgs_ctx* c, int32_t n, const char* bytes, const int64_t* off, const owgs_ack_out* out,
+                             int64_t now_ms, int32_t apply, int32_t out_summary[3]) {
+    if (!c || n < 0) return OWGS_EINVAL;
+    if (n > 0 && (!bytes || !off || !out || !out->kind || !out->invoker || !out->ticket || !out->flags || !out->aid ||
+                  !out->resp_off || !out->resp_len))
+        return OWGS_EINVAL;
+    if (out_summary) {
+        const int rc = feed_args_ok(c, now_ms, apply);
+        if (rc) return rc;
+    } else if (now_ms != 0 || apply != 0) {
+        return c->fail(OWGS_EINVAL, "result acks: now_ms / apply without a summary");
+    }
+    for (int32_t i = 0; i < n; ++i)
+        if (off[i + 1] < off[i] || off[i] < 0) return c->fail(OWGS_EINVAL, "offsets");
+    OWGS_ENTER(c);
+    if (out_summary) {
+        const int rc = feed_reserve(c, n);
+        if (rc) return rc;
+    }
+    if (n == 0)
+        return out_summary ? feed_acks(c, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, now_ms, apply,
+                                       out_summary)
+                           : OWGS_OK;
+    hipStream_t st = c->stream;
+    {
+        const int ro_ = order_on(c, st);
+        if (ro_) return ro_;
+    }
+    const size_t m = (size_t)n, blk_bytes = m * 38;
+    if (c->r_pin_bytes < blk_bytes) {
+        if (c->r_pin) (void)hipHostFree(c->r_pin);
+        c->r_pin = nullptr;
+        c->r_pin_bytes = 0;
+        HIPCHK(c, hipHostMalloc(&c->r_pin, blk_bytes * 2, hipHostMallocDefault));
+        c->r_pin_bytes = blk_bytes * 2;
+    }
+    HIPCHK(c, c->r_blk.reserve(blk_bytes));
+    unsigned long long* b_aid = (unsigned long long*)c->r_blk.p;
+    int64_t* b_roff = (int64_t*)(b_aid + 2 * m);
+    int32_t* b_inv = (int32_t*)(b_roff + m);
+    int32_t* b_tick = b_inv + m;
+    int32_t* b_rlen = b_tick + m;
+    uint8_t* b_kind = (uint8_t*)(b_rlen + m);
+    uint8_t* b_flags = b_kind + m;
+    const size_t nb = (size_t)(off[n] - off[0]);
+    std::vector<int64_t> o(m + 1);
+    for (int32_t i = 0; i <= n; ++i) o[i] = off[i] - off[0];
+    HIPCHK(c, c->k_bytes.reserve(nb + 32));
+    HIPCHK(c, hipMemsetAsync(c->k_bytes.p + nb, 0, 32, st));
+    if (nb) HIPCHK(c, hipMemcpyAsync(c->k_bytes.p, bytes + off[0], nb, hipMemcpyHostToDevice, st));
+    HIPCHK(c, upload(c->k_off, o.data(), o.size(), st));
+    HIPCHK(c, c->k_key.reserve(m));
+    HIPCHK(c, c->k_info.reserve(m));
+    HIPCHK(c, c->k_inst.reserve(m));
+    OwgsAckParseResultArgs p{};
+    p.bytes = c->k_bytes.p;
+    p.off = c->k_off.p;
+    p.n = n;
+    p.health_start_ms = c->health_ms;
+    p.forced = nullptr;
+    p.key = c->k_key.p;
+    p.inst = b_inv;
+    p.info = c->k_info.p;
+    p.off_base = off[0];
+    p.resp_off = b_roff;
+    p.resp_len = b_rlen;
+    HIPCHK(c, owgs_launch_ack_parse_results(&p, st));
+    HIPCHK(c, hipMemcpyAsync(c->k_inst.p, b_inv, m * 4, hipMemcpyDeviceToDevice, st));
+    AckResultTail rt{b_aid, c->r_pin, c->r_blk.p, blk_bytes};
+    int rc = ack_complete(c, n, b_kind, b_tick, b_flags, st, &rt);
+    if (rc) return rc;
+    const char* P = (const char*)c->r_pin;
+    memcpy(out->aid, P, m * 16);
+    memcpy(out->resp_off, P + m * 16, m * 8);
+    memcpy(out->invoker, P + m * 24, m * 4);
+    memcpy(out->ticket, P + m * 28, m * 4);
+    memcpy(out->resp_len, P + m * 32, m * 4);
+    memcpy(out->kind, P + m * 36, m);
+    memcpy(out->flags, P + m * 37, m);
+    if (!out_summary) return OWGS_OK;
+    // an accepted ResultMessage (OWGS_ACK_RESULT) is neither RELEASED nor HEALTH: the compaction feeds nothing for it
+    return feed_acks(c, n, out->kind, out->invoker, b_kind, b_inv, b_flags, c->k_info.p, now_ms, apply, out_summary);
 }
 
 int owgs_process_pings(owgs_ctx* c, int32_t n, const char* bytes, const int64_t* off, const int64_t* t_ms,

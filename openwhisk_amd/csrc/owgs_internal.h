@@ -584,6 +584,15 @@ struct OwgsAckParseArgs {
     int32_t* inst;               // out: invoker instance (BigDecimal.intValue)
     uint8_t* info;               // out: kind | isSystemError << 4 | health tid << 5 | forced << 6
 };
+// owgs_process_result_acks: the parser's RESULTS instantiation also takes messages with a `response` member.  Its
+// record uses the two free bits of info (3: an accepted message carries a result, 7: the result is an object) and a
+// kind of its own for an accepted ResultMessage, which completes nothing.
+#define OWGS_ACK_RESULT_MSG 7       // = OWGS_ACK_RESULT: the outcome is the parse kind
+struct OwgsAckParseResultArgs : OwgsAckParseArgs {
+    long long off_base;          // off[] counts from here in the caller's bytes[]
+    int64_t* resp_off;           // out: start of the accepted message's `response` value in the caller's bytes[], else 0
+    int32_t* resp_len;           // out: its length in bytes
+};
 
 // activationSlots (CLB:60): open addressing over cap (power of two) slots
 struct OwgsActTable {
@@ -686,6 +695,8 @@ struct OwgsAckCompleteArgs {
     int32_t* out_ticket;
     unsigned long long* counters;               // [OWGS_CNT_WORDS]: entries removed, MB of the removed entries
     OwgsInflight fl;
+    int32_t results;             // owgs_process_result_acks: OWGS_ACK_RESULT_MSG records look their entry up (0: the
+                                 // records hold none)
 };
 
 // The entitlement throttle gate (owgs_admit_resolve_kernel, owgs_inflight.hip); every pointer is device memory.
