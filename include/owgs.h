@@ -717,6 +717,90 @@ typedef struct owgs_msg_out {      /* the outputs of owgs_serialize_activations,
 int owgs_publish_activations(owgs_ctx* ctx, const owgs_publish_io* io, const owgs_msg_batch* msgs, owgs_msg_out* mo,
                              int64_t out_summary[8]);
 
+/* ---- gated publish: the throttle gate feeds schedule in one call ----
+ * Replaces: the two steps every invoke takes -- EntitlementProvider.checkThrottles (Entitlement.scala:197-202, 354-381)
+ * and, for what it lets through, ShardingContainerPoolBalancer.publish (PrimitiveActions.scala:152-185, SCPB:257-317)
+ * -- for a drained batch, as one call: owgs_admit_batch followed by owgs_publish_activations over the admitted actions,
+ * without the verdicts coming back to the host in between.
+ *
+ * Sequential definition.
+ *   1. Gate: out_verdict, out_rate_count, out_rate_limit, out_conc_count, out_conc_limit and the rate records are exactly
+ *      what owgs_admit_batch gives for (n, ns, kind, t_ms, rate_override, conc_override), its assumption included: an
+ *      admitted action counts against the later actions of its namespace in this batch.
+ *   2. Publish: let adm be the indices, in array order, of the items that are actions (kind bit 0 clear) with verdict
+ *      OWGS_ADMIT_OK, m = |adm|.  out_invoker, out_flags, out_ticket, out_existed at those indices, the activationSlots
+ *      entries, the in-flight books, the armed deadlines and (with msgs) the messages are exactly those of
+ *      owgs_publish_activations over the sub-batch action[adm], aid[adm], ns[adm], ticket[adm], time_limit_ms[adm] with
+ *      the same now_ms.  The RNG sequence of the k-th admitted action is seq[adm[k]] when seq is given and seq_base + k
+ *      otherwise: the rank among the admitted actions, not the array index.  The namespace of the books is the item's
+ *      gate namespace.
+ *   3. Every other item -- a trigger, a rate-rejected or a concurrent-rejected item -- has out_invoker =
+ *      OWGS_NOT_PUBLISHED, out_flags = 0, out_ticket = -1, out_existed = 0.  It touches neither the slot state, the table,
+ *      the books nor the messages and cannot be the first tracker of an id; its action, aid, ticket and time_limit_ms
+ *      entries are not interpreted (time_limit_ms is still range-checked for every item that is an action).
+ * Arm order among the placed items is array order; the context's arm counter advances by n.
+ * Messages: msgs is indexed by item, msgs->n == n, msgs->invoker and msgs->aid must be NULL; only placed items produce
+ * a message, and out_order holds item indices.
+ *
+ * The gate's assumption.  An admitted action that gets no invoker (OWGS_NONE, OWGS_THROW_INDEX) is not tracked, yet
+ * step 1 has already counted it: conc_count of the later items of its namespace IN THIS BATCH includes it, so such an
+ * item may come back OWGS_ADMIT_CONCURRENT where the reference, running item by item, would have admitted it.
+ * out_summary[4] + out_summary[5] is the number of admitted actions for which this happened; 0 means the verdicts are
+ * the reference's.  The books themselves are exact (only placed items are counted), so the next call starts right.
+ *
+ * out_summary: [0..7] as owgs_publish_activations ([0] placed, [1] entries created, [2] / [3] overload fallbacks of
+ * managed / blackbox actions, [4] admitted actions with OWGS_NONE, [5] with OWGS_THROW_INDEX, [6] stages completed (0,
+ * 2 or 3), [7] 0); [8] admitted actions (m); [9] items with verdict OWGS_ADMIT_RATE; [10] items with verdict
+ * OWGS_ADMIT_CONCURRENT; [11] triggers with verdict OWGS_ADMIT_OK; [12] how often the call waited on its stream before
+ * its outputs were on the host: 1 on an on-chip context (the one block copy: m never comes to the host before it), 2 on
+ * a large-state context (the verdicts come back before the engine, whose run takes host arrays).  Not counted, both as
+ * in owgs_publish_activations: the waits inside the large-state engine's run and the download of the message bytes,
+ * and the rare growth of a table -- the activationSlots rehash, or the NestedSemaphore map's overflow, whose size bound
+ * this call advances by n rather than m, so that a context whose batches are mostly rejected reads the exact entry
+ * count back (one synchronisation) somewhat earlier than owgs_publish_activations would.  When the engine step fails
+ * and the gate outputs are handed out (below), [12] counts the wait that brought them.  [13..15] 0.
+ *
+ * Failures.  Every argument error of owgs_admit_batch and of owgs_publish_activations is refused before any device
+ * state changes -- the rate records included -- with that call's code; the action handle is checked only for items
+ * that are actions.  n == 0 is OWGS_OK and changes nothing.  An engine error leaves the rate records charged and the
+ * five gate outputs valid (the reference charges the rate before publish can fail); nothing is tracked or written.
+ * Any other failure after the gate was queued -- a HIP runtime error (OWGS_EDEVICE) or a failed allocation -- also
+ * leaves the rate records charged, but hands out no output at all: the caller reads the records with owgs_rate_state.
+ * Failures the message stage finds on the device behave as in owgs_publish_activations: out_summary[6] = 2, the
+ * entries stay, and the caller serialises again with owgs_serialize_activations(invoker = out_invoker with the
+ * negative values as they are). */
+#define OWGS_NOT_PUBLISHED (-3)   /* out_invoker of an item the gate did not hand to publish */
+typedef struct owgs_invoke_io {
+    int32_t n;
+    /* gate inputs, exactly those of owgs_admit_batch */
+    const int32_t* ns;
+    const uint8_t* kind;
+    const int64_t* t_ms;
+    const int32_t* rate_override;  /* may be NULL as there */
+    const int32_t* conc_override;
+    /* publish inputs, exactly those of owgs_publish_io; read only for items that are actions */
+    const int32_t* action;
+    const uint64_t* seq;           /* [n] by item, or NULL: seq_base + rank among the admitted actions */
+    uint64_t seq_base;
+    const uint64_t* aid;           /* [2n] */
+    const int32_t* ticket;
+    const int64_t* time_limit_ms;
+    int64_t now_ms;
+    /* outputs, all [n] */
+    uint8_t* out_verdict;
+    int32_t* out_rate_count;
+    int32_t* out_rate_limit;
+    int32_t* out_conc_count;
+    int32_t* out_conc_limit;
+    int32_t* out_invoker;
+    uint8_t* out_flags;
+    int32_t* out_ticket;
+    uint8_t* out_existed;
+} owgs_invoke_io;
+
+int owgs_invoke_activations(owgs_ctx* ctx, const owgs_invoke_io* io, const owgs_msg_batch* msgs, owgs_msg_out* mo,
+                            int64_t out_summary[16]);
+
 /* Duration of the last owgs_engine_kernel launch (HIP events recorded on its stream right before and after it);
  * waits for it to finish.  Measurement hook for bench.py's roofline. */
 int owgs_engine_ms(owgs_ctx* ctx, float* ms);

@@ -63,6 +63,12 @@ object OwgsNative {
    *  the batcher below keeps calling processBatch. */
   @native def publishActivations(ctx: Long, in: ByteBuffer, out: ByteBuffer, n: Int, hasNs: Boolean, seqBase: Long,
                                  nowMs: Long): Int
+  /** owgs_invoke_activations (two-stage form) over direct buffers (native byte order), layout in InvokeBuffers: the
+   *  entitlement throttle gate (Entitlement.scala:197-202, 354-381) over the drained items, then publishActivations'
+   *  work for the actions it admitted, in one device call.  outInvoker is -3 (OWGS_NOT_PUBLISHED) for a trigger and
+   *  for a rejected item; the publishes' overload-RNG sequence numbers are seqBase + the rank among the admitted
+   *  actions.  For an EntitlementProvider that defers checkThrottles to the batching thread (INTEGRATION.md). */
+  @native def invokeActivations(ctx: Long, in: ByteBuffer, out: ByteBuffer, n: Int, seqBase: Long, nowMs: Long): Int
   /** owgs_release_actions: handles of cold fqn@version keys (none of their activations in flight) */
   @native def releaseActions(ctx: Long, handles: Array[Int], n: Int): Int
   /** owgs_track_activations_timed: setupActivation's getOrElseUpdate with the entry's invoker and time limit, so that
@@ -160,6 +166,20 @@ final class PublishBuffers {
   def ensure(n: Int): Unit = {
     if (in.capacity < 36 * n) in = ByteBuffer.allocateDirect(72 * n).order(ByteOrder.nativeOrder())
     if (out.capacity < 64 + 10 * n) out = ByteBuffer.allocateDirect(128 + 20 * n).order(ByteOrder.nativeOrder())
+  }
+}
+
+/** The direct buffers of one invokeActivations call (owgs_jni.c reads the same layout):
+ *  in  = aid[2 n] (hi, lo longs), timeLimitMs[n], tMs[n] (longs), action[n], ns[n], ticket[n], rateOverride[n],
+ *        concOverride[n] (ints), kind[n] (bytes: bit 0 trigger, bit 1 / 2 the item's rate / concurrent override is set);
+ *  out = summary[16] (longs), rateCount[n], rateLimit[n], concCount[n], concLimit[n], outInvoker[n], outTicket[n]
+ *        (ints), verdict[n] (0 admitted, 1 TooManyRequests by rate, 2 by concurrency), outFlags[n], outExisted[n]. */
+final class InvokeBuffers {
+  var in: ByteBuffer = ByteBuffer.allocateDirect(1 << 16).order(ByteOrder.nativeOrder())
+  var out: ByteBuffer = ByteBuffer.allocateDirect(1 << 15).order(ByteOrder.nativeOrder())
+  def ensure(n: Int): Unit = {
+    if (in.capacity < 53 * n) in = ByteBuffer.allocateDirect(106 * n).order(ByteOrder.nativeOrder())
+    if (out.capacity < 128 + 27 * n) out = ByteBuffer.allocateDirect(256 + 54 * n).order(ByteOrder.nativeOrder())
   }
 }
 

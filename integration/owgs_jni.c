@@ -163,6 +163,49 @@ JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00
     return owgs_publish_activations(CTX(h), &io, NULL, NULL, (int64_t*)po);
 }
 
+/* the throttle gate and publish for one drained batch (owgs_invoke_activations, two-stage form: msgs = NULL) over
+ * direct buffers, layout as InvokeBuffers in the Scala shim:
+ * in  = aid[2 n] (hi, lo), time_limit_ms[n], t_ms[n] (int64), action[n], ns[n], ticket[n], rate_override[n],
+ *       conc_override[n] (int32), kind[n] (bytes); an override entry is read only where its kind bit is set;
+ * out = summary[16] (int64), rate_count[n], rate_limit[n], conc_count[n], conc_limit[n], out_invoker[n], out_ticket[n]
+ *       (int32), verdict[n], out_flags[n], out_existed[n] (bytes).
+ * Sequence numbers: seq_base + the rank among the admitted actions (the shim numbers what it publishes). */
+JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_invokeActivations(
+    JNIEnv* env, jobject self, jlong h, jobject in, jobject out, jint n, jlong seq_base, jlong now_ms) {
+    if (!in || !out || n < 0) return OWGS_EINVAL;
+    char* pi = (char*)(*env)->GetDirectBufferAddress(env, in);
+    char* po = (char*)(*env)->GetDirectBufferAddress(env, out);
+    if (!pi || !po) return OWGS_EINVAL;  /* not direct buffers */
+    if ((*env)->GetDirectBufferCapacity(env, in) < 53 * (jlong)n ||
+        (*env)->GetDirectBufferCapacity(env, out) < 128 + 27 * (jlong)n)
+        return OWGS_EINVAL;
+    owgs_invoke_io io;
+    memset(&io, 0, sizeof io);
+    io.n = n;
+    io.aid = (const uint64_t*)pi;
+    io.time_limit_ms = (const int64_t*)(pi + 16 * (jlong)n);
+    io.t_ms = io.time_limit_ms + n;
+    io.action = (const int32_t*)(pi + 32 * (jlong)n);
+    io.ns = io.action + n;
+    io.ticket = io.action + 2 * (jlong)n;
+    io.rate_override = io.action + 3 * (jlong)n;
+    io.conc_override = io.action + 4 * (jlong)n;
+    io.kind = (const uint8_t*)(pi + 52 * (jlong)n);
+    io.seq = NULL;
+    io.seq_base = (uint64_t)seq_base;
+    io.now_ms = now_ms;
+    io.out_rate_count = (int32_t*)(po + 128);
+    io.out_rate_limit = io.out_rate_count + n;
+    io.out_conc_count = io.out_rate_count + 2 * (jlong)n;
+    io.out_conc_limit = io.out_rate_count + 3 * (jlong)n;
+    io.out_invoker = io.out_rate_count + 4 * (jlong)n;
+    io.out_ticket = io.out_rate_count + 5 * (jlong)n;
+    io.out_verdict = (uint8_t*)(po + 128 + 24 * (jlong)n);
+    io.out_flags = io.out_verdict + n;
+    io.out_existed = io.out_verdict + 2 * (jlong)n;
+    return owgs_invoke_activations(CTX(h), &io, NULL, NULL, (int64_t*)po);
+}
+
 /* handles of cold fqn@version keys (owgs_release_actions) */
 JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_releaseActions(
     JNIEnv* env, jobject self, jlong h, jintArray handles, jint n) {

@@ -18,6 +18,7 @@ HEADER = os.path.join(ROOT, "include", "owgs.h")
 OK = 0
 EINVAL, ENOMEM, EDEVICE, ERANGE, ENOENT = -22, -12, -5, -34, -2
 NONE, THROW_INDEX = -1, -2
+NOT_PUBLISHED = -3  # owgs_invoke_activations: out_invoker of an item the gate did not hand to publish
 FLAG_OVERLOAD = 1
 REL_NOSUCHELEMENT, REL_OVERFLOW, REL_NOENTRY = 1, 2, 4
 ACK_FAIL, ACK_JVM, ACK_UNSUPPORTED, ACK_RELEASED, ACK_HEALTH, ACK_NOENTRY, ACK_FORCED_NOENTRY = range(7)
@@ -70,6 +71,17 @@ class owgs_publish_io(C.Structure):
     _fields_ = [("n", C.c_int32), ("action", C.c_void_p), ("seq", C.c_void_p), ("seq_base", C.c_uint64),
                 ("aid", C.c_void_p), ("ns", C.c_void_p), ("ticket", C.c_void_p), ("time_limit_ms", C.c_void_p),
                 ("now_ms", C.c_int64), ("out_invoker", C.c_void_p), ("out_flags", C.c_void_p),
+                ("out_ticket", C.c_void_p), ("out_existed", C.c_void_p)]
+
+
+class owgs_invoke_io(C.Structure):
+    """include/owgs.h: owgs_invoke_io (the gate's and publish's inputs and the nine outputs of owgs_invoke_activations)."""
+    _fields_ = [("n", C.c_int32), ("ns", C.c_void_p), ("kind", C.c_void_p), ("t_ms", C.c_void_p),
+                ("rate_override", C.c_void_p), ("conc_override", C.c_void_p), ("action", C.c_void_p),
+                ("seq", C.c_void_p), ("seq_base", C.c_uint64), ("aid", C.c_void_p), ("ticket", C.c_void_p),
+                ("time_limit_ms", C.c_void_p), ("now_ms", C.c_int64), ("out_verdict", C.c_void_p),
+                ("out_rate_count", C.c_void_p), ("out_rate_limit", C.c_void_p), ("out_conc_count", C.c_void_p),
+                ("out_conc_limit", C.c_void_p), ("out_invoker", C.c_void_p), ("out_flags", C.c_void_p),
                 ("out_ticket", C.c_void_p), ("out_existed", C.c_void_p)]
 
 
@@ -132,6 +144,7 @@ def lib() -> C.CDLL:
         "owgs_serialize_activations": (C.c_int, [P, P, i32, P, C.c_int64, P, P, P, P, P]),
         "owgs_serialize_activations_device": (C.c_int, [P, P, i32, P, C.c_int64, P, P, P, P, P, P]),
         "owgs_publish_activations": (C.c_int, [P, P, P, P, P]),
+        "owgs_invoke_activations": (C.c_int, [P, P, P, P, P]),
         "owgs_health_read": (C.c_int, [P, i32, P, P, P, P, P, P]),
         "owgs_process_pings": (C.c_int, [P, i32, P, P, P, C.c_int64, i32, P, P, P, P]),
         "owgs_process_acks_supervised": (C.c_int, [P, i32, P, P, P, P, P, P, C.c_int64, i32, P]),

@@ -76,6 +76,39 @@ _LARGE_STATS = ("large_spec", "alone", "run_plain", "run_conc", "kept_plain", "k
                 "none_kind", "throw_kind", "rel_groups_par", "rel_groups_ordered", "launches", "resumes")
 
 
+def _msg_io(n: int, msgs: dict, who: str):
+    """The owgs_msg_batch (without invoker and aid) and the owgs_msg_out of a call that serialises its own decisions,
+    from the keyword arguments of serialize_activations: (batch, out struct, arrays to keep alive, output buffers)."""
+    from ._lib import owgs_msg_batch, owgs_msg_out
+    tm = np.ascontiguousarray(msgs["tmpl"], dtype=np.int32)
+    tb, to = _blob(msgs["tids"])
+    ts = np.ascontiguousarray(msgs["tid_start"], dtype=np.int64)
+    mf = np.ascontiguousarray(msgs["flags"], dtype=np.uint8)
+    if not (len(tm) == len(ts) == len(mf) == len(to) - 1 == n):
+        raise ValueError(f"{who}: msgs arrays of different lengths")
+    keep = [tm, tb, to, ts, mf]
+    B = owgs_msg_batch(n, None, _p(tm), None, _p(tb), _p(to), _p(ts), _p(mf))
+    if msgs.get("contents") is not None:
+        cb, co = _blob(msgs["contents"])
+        keep += [cb, co]
+        B.content, B.content_off = _p(cb), _p(co)
+    if msgs.get("causes") is not None:
+        cz = np.ascontiguousarray(msgs["causes"], dtype=np.uint64).reshape(-1)
+        keep.append(cz)
+        B.cause = _p(cz)
+    if msgs.get("traces") is not None:
+        rb, ro = _blob(msgs["traces"])
+        keep += [rb, ro]
+        B.trace, B.trace_off = _p(rb), _p(ro)
+    nt, cap = int(msgs["n_topics"]), int(msgs["cap"])
+    off = np.zeros(n + 1, np.int64)
+    order = np.zeros(max(n, 1), np.int32)
+    topic = np.zeros(nt + 1, np.int32)
+    out = C.create_string_buffer(max(cap, 1))
+    mo = owgs_msg_out(nt, C.cast(out, C.c_void_p), cap, _p(off), _p(order), _p(topic), 0, 0)
+    return B, mo, keep, (out, off, order, topic)
+
+
 class GpuShardingContainerPoolBalancer:
     """One controller shard (SCPB:147-332) backed by the MI355X engine."""
 
@@ -649,7 +682,7 @@ class GpuShardingContainerPoolBalancer:
         Returns (invoker, flags, ticket, existed, summary), plus (bytes, out_off, out_order, topic_start) with msgs.
         A failure the message stage finds raises OwgsError with `.partial` = the five values above (stages 1 and 2 are
         done) and `.total` = the bytes needed."""
-        from ._lib import owgs_msg_batch, owgs_msg_out, owgs_publish_io
+        from ._lib import owgs_publish_io
         a = np.ascontiguousarray(actions, dtype=np.int32)
         n = len(a)
         tk = np.ascontiguousarray(tickets, dtype=np.int32)
@@ -678,32 +711,7 @@ class GpuShardingContainerPoolBalancer:
         if msgs is None:
             self._chk(self._L.owgs_publish_activations(self._h, C.byref(io), None, None, _p(summ)))
             return inv[:n], fl[:n], ot[:n], ex[:n], summ
-        tm = np.ascontiguousarray(msgs["tmpl"], dtype=np.int32)
-        tb, to = _blob(msgs["tids"])
-        ts = np.ascontiguousarray(msgs["tid_start"], dtype=np.int64)
-        mf = np.ascontiguousarray(msgs["flags"], dtype=np.uint8)
-        if not (len(tm) == len(ts) == len(mf) == len(to) - 1 == n):
-            raise ValueError("publish_activations: msgs arrays of different lengths")
-        keep = [tm, tb, to, ts, mf]
-        B = owgs_msg_batch(n, None, _p(tm), None, _p(tb), _p(to), _p(ts), _p(mf))
-        if msgs.get("contents") is not None:
-            cb, co = _blob(msgs["contents"])
-            keep += [cb, co]
-            B.content, B.content_off = _p(cb), _p(co)
-        if msgs.get("causes") is not None:
-            cz = np.ascontiguousarray(msgs["causes"], dtype=np.uint64).reshape(-1)
-            keep.append(cz)
-            B.cause = _p(cz)
-        if msgs.get("traces") is not None:
-            rb, ro = _blob(msgs["traces"])
-            keep += [rb, ro]
-            B.trace, B.trace_off = _p(rb), _p(ro)
-        nt, cap = int(msgs["n_topics"]), int(msgs["cap"])
-        off = np.zeros(n + 1, np.int64)
-        order = np.zeros(max(n, 1), np.int32)
-        topic = np.zeros(nt + 1, np.int32)
-        out = C.create_string_buffer(max(cap, 1))
-        mo = owgs_msg_out(nt, C.cast(out, C.c_void_p), cap, _p(off), _p(order), _p(topic), 0, 0)
+        B, mo, keep, (out, off, order, topic) = _msg_io(n, msgs, "publish_activations")
         rc = self._L.owgs_publish_activations(self._h, C.byref(io), C.byref(B), C.byref(mo), _p(summ))
         del keep
         if rc < 0:
@@ -714,6 +722,61 @@ class GpuShardingContainerPoolBalancer:
             raise e
         mm = mo.m
         return inv[:n], fl[:n], ot[:n], ex[:n], summ, (out.raw[:mo.total], off[:mm + 1], order[:mm], topic)
+
+    def invoke_activations(self, ns, kind, t_ms, actions, aids, tickets, time_limit_ms, now_ms: int,
+                           rate_override=None, conc_override=None, seq=None, seq_base: int = 0,
+                           msgs: dict | None = None):
+        """The throttle gate and publish for a drained batch in one call (owgs_invoke_activations): `admit_batch` over
+        (ns, kind, t_ms, overrides), then `publish_activations` over the items that are actions with verdict ADMIT_OK,
+        in array order, without the verdicts coming back in between.  Every other item gets invoker NOT_PUBLISHED,
+        flags 0, ticket -1, existed 0; actions / aids / tickets / time_limit_ms are read only for items that are
+        actions.  seq: one value per item, or None: seq_base + the rank among the admitted actions.
+        Returns (verdict, rate_count, rate_limit, conc_count, conc_limit, invoker, flags, ticket, existed, summary),
+        plus (bytes, out_off, out_order, topic_start) with msgs (out_order holds item indices).  summary: [0..7] as
+        publish_activations, [8] admitted actions, [9] rate-rejected, [10] concurrent-rejected items, [11] admitted
+        triggers, [12] waits on the stream.  Errors, `.partial` (the ten values) and `.total` as publish_activations."""
+        from ._lib import owgs_invoke_io
+        h = np.ascontiguousarray(ns, dtype=np.int32)
+        n = len(h)
+        kd = np.ascontiguousarray(kind, dtype=np.uint8)
+        t = np.ascontiguousarray(t_ms, dtype=np.int64)
+        a = np.ascontiguousarray(actions, dtype=np.int32)
+        tk = np.ascontiguousarray(tickets, dtype=np.int32)
+        tl = np.ascontiguousarray(time_limit_ms, dtype=np.int64)
+        ro = None if rate_override is None else np.ascontiguousarray(rate_override, dtype=np.int32)
+        co = None if conc_override is None else np.ascontiguousarray(conc_override, dtype=np.int32)
+        sq = None if seq is None else np.ascontiguousarray(seq, dtype=np.uint64)
+        if any(len(x) != n for x in (kd, t, a, aids, tk, tl, ro, co, sq) if x is not None):
+            raise ValueError("invoke_activations: arrays of different lengths")
+        w = np.zeros(max(2 * n, 2), dtype=np.uint64)
+        vals = [int(x, 16) for x in aids]
+        w[0:2 * n:2] = [v >> 64 for v in vals]
+        w[1:2 * n:2] = [v & (2**64 - 1) for v in vals]
+        m = max(n, 1)
+        verdict, fl, ex = (np.zeros(m, dtype=np.uint8) for _ in range(3))
+        rc_, rl, cc, cl, inv, ot = (np.zeros(m, dtype=np.int32) for _ in range(6))
+        summ = np.zeros(16, dtype=np.int64)
+        z32, z64 = np.zeros(1, np.int32), np.zeros(1, np.int64)
+        io = owgs_invoke_io(n, _p(h if n else z32), _p(kd if n else z32), _p(t if n else z64),
+                            None if ro is None else _p(ro if n else z32), None if co is None else _p(co if n else z32),
+                            _p(a if n else z32), None if sq is None else _p(sq if n else z64), int(seq_base), _p(w),
+                            _p(tk if n else z32), _p(tl if n else z64), int(now_ms), _p(verdict), _p(rc_), _p(rl),
+                            _p(cc), _p(cl), _p(inv), _p(fl), _p(ot), _p(ex))
+        res = (verdict[:n], rc_[:n], rl[:n], cc[:n], cl[:n], inv[:n], fl[:n], ot[:n], ex[:n], summ)
+        if msgs is None:
+            self._chk(self._L.owgs_invoke_activations(self._h, C.byref(io), None, None, _p(summ)))
+            return res
+        B, mo, keep, (out, off, order, topic) = _msg_io(n, msgs, "invoke_activations")
+        rc = self._L.owgs_invoke_activations(self._h, C.byref(io), C.byref(B), C.byref(mo), _p(summ))
+        del keep
+        if rc < 0:
+            e = OwgsError(rc, (self._L.owgs_last_error(self._h) or b"").decode())
+            if summ[6] == 2:
+                e.partial = res
+                e.total = int(mo.total)
+            raise e
+        mm = mo.m
+        return res + ((out.raw[:mo.total], off[:mm + 1], order[:mm], topic),)
 
     def release_invoker(self, invokers, actions) -> np.ndarray:
         """releaseInvoker (SCPB:327-331) per completion; returns release flags."""

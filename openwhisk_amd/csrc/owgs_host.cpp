@@ -134,6 +134,8 @@ extern "C" hipError_t owgs_launch_relmeta(int32_t n, const int32_t* act, const i
                                           const int32_t* act_maxc, const int32_t* act_slot, int32_t* mem,
                                           int32_t* maxc, int32_t* slot, hipStream_t s);
 extern "C" hipError_t owgs_launch_w_update(const OwgsWUpdateArgs* a, hipStream_t s);
+extern "C" hipError_t owgs_launch_invoke_compact(const OwgsInvokeCompact* a, hipStream_t st);
+extern "C" hipError_t owgs_launch_invoke_gate(const OwgsInvokeGate* g, hipStream_t st);
 extern "C" size_t owgs_resident_image_bytes(int32_t n_slots, int32_t n_ids);
 extern "C" hipError_t owgs_launch_resident(const OwgsResArgs* a, size_t lds_bytes, hipStream_t s);
 extern "C" hipError_t owgs_launch_w_relgather(const int64_t* rel_aid, int32_t n, const int32_t* out_inv,
@@ -367,6 +369,11 @@ struct owgs_ctx {
     DevBuf<int32_t> p_minv;
     void* p_pin = nullptr;
     size_t p_pin_bytes = 0;
+    // owgs_invoke_activations (owgs_invoke.hip): the items' action handles, sequence numbers and override arrays as
+    // uploaded, the maps between an item and its rank among the admitted actions, the compaction's per-block counts
+    // (its output block and pinned block are p_blk / p_pin)
+    DevBuf<int32_t> v_act, v_map, v_rank, v_bcnt, v_ov0, v_ov1;
+    DevBuf<u64> v_seq;
     // owgs_process_result_acks: its seven output arrays as one device block, and the pinned block they come back in
     DevBuf<uint8_t> r_blk;
     void* r_pin = nullptr;
@@ -1954,6 +1961,9 @@ void owgs_destroy(owgs_ctx* c) {
     c->p_placed.release();
     c->p_blk.release();
     c->p_minv.release();
+    DevBuf<int32_t>* vs[] = {&c->v_act, &c->v_map, &c->v_rank, &c->v_bcnt, &c->v_ov0, &c->v_ov1};
+    for (auto* b : vs) b->release();
+    c->v_seq.release();
     if (c->p_pin) (void)hipHostFree(c->p_pin);
     c->p_pin = nullptr;
     c->r_blk.release();
@@ -4361,6 +4371,23 @@ int owgs_set_throttle_limits(owgs_ctx* c, int32_t invokes_per_minute, int32_t fi
     return OWGS_OK;
 }
 
+// The gate's arguments that come from the context: the system defaults, the cluster size, the books and the rate
+// records.  The caller adds the batch's inputs (kind, t_ms, overrides) and where the five outputs go; shared by
+// owgs_admit_batch and owgs_invoke_activations.
+static OwgsAdmitArgs admit_args(const owgs_ctx* c, int32_t n) {
+    OwgsAdmitArgs A{};
+    A.n = n;
+    A.def_invoke = c->lim_invoke;
+    A.def_fire = c->lim_fire;
+    A.def_conc = c->lim_conc;
+    A.cluster = c->cluster;  // loadBalancer.clusterSize (SCPB:254)
+    A.active = c->d_ns_active.p;
+    A.rate_min = c->d_rate_min.p;
+    A.rate_cnt = c->d_rate_cnt.p;
+    A.ns_cap = c->ns_cap;
+    return A;
+}
+
 int owgs_admit_batch(owgs_ctx* c, int32_t n, const int32_t* ns, const uint8_t* kind, const int64_t* t_ms,
                      const int32_t* rate_override, const int32_t* conc_override, uint8_t* out_verdict,
                      int32_t* out_rate_count, int32_t* out_rate_limit, int32_t* out_conc_count,
@@ -4408,20 +4435,11 @@ int owgs_admit_batch(owgs_ctx* c, int32_t n, const int32_t* ns, const uint8_t* k
         HIPCHK(c, hipHostMalloc(&c->g_pin, out_bytes * 2, hipHostMallocDefault));
         c->g_pin_bytes = out_bytes * 2;
     }
-    OwgsAdmitArgs A{};
-    A.n = n;
+    OwgsAdmitArgs A = admit_args(c, n);
     A.kind = c->k_kind.p;
     A.t_ms = c->k_off.p;
     A.rate_ov = rate_override ? c->k_r0.p : nullptr;
     A.conc_ov = conc_override ? c->k_r1.p : nullptr;
-    A.def_invoke = c->lim_invoke;
-    A.def_fire = c->lim_fire;
-    A.def_conc = c->lim_conc;
-    A.cluster = c->cluster;  // loadBalancer.clusterSize (SCPB:254)
-    A.active = c->d_ns_active.p;
-    A.rate_min = c->d_rate_min.p;
-    A.rate_cnt = c->d_rate_cnt.p;
-    A.ns_cap = c->ns_cap;
     A.out_verdict = (uint8_t*)(c->g_out.p + 4 * N);
     A.out_rate_count = c->g_out.p;
     A.out_rate_limit = c->g_out.p + N;
@@ -5162,6 +5180,55 @@ int owgs_serialize_activations_device(owgs_ctx* c, const owgs_msg_batch* b, int3
 }
 
 // ------------------------------------------------------------------------------------------ publish end to end
+// Where the four publish arrays of an output block lie in pinned memory (the header is at c->p_pin).
+struct PublishBlock {
+    const char *inv, *ticket, *flags, *existed;
+};
+
+// What owgs_publish_activations and owgs_invoke_activations do once their output block has arrived in c->p_pin: the
+// engine's error word as the gate kernel saw it, the four publish outputs handed out, the host's share of the books
+// (the table's fill, CLB:121-125 for every placed item), out_summary[0..6], the table-full scan and, with msgs, the
+// message stage's verdict and the download of its bytes.  who names the entry point in the error texts.
+static int publish_tail(owgs_ctx* c, const char* who, int32_t n, const PublishBlock& B, int32_t* out_invoker,
+                        uint8_t* out_flags, int32_t* out_ticket, uint8_t* out_existed, const owgs_msg_batch* msgs,
+                        owgs_msg_out* mo, int64_t* out_summary, hipStream_t st) {
+    const unsigned long long* H = (const unsigned long long*)c->p_pin;
+    if (H[OWGS_PUB_ERR]) {  // the engine failed: the gate placed nothing, the table and the books are untouched
+        const int rc = check_err_word(c);
+        return rc ? rc : c->fail(OWGS_EDEVICE, (std::string(who) + ": the engine's error word was set").c_str());
+    }
+    memcpy(out_invoker, B.inv, (size_t)n * 4);
+    memcpy(out_ticket, B.ticket, (size_t)n * 4);
+    memcpy(out_flags, B.flags, (size_t)n);
+    memcpy(out_existed, B.existed, (size_t)n);
+    const long long placed = (long long)H[OWGS_PUB_PLACED], inserted = (long long)H[OWGS_PUB_CNT + OWGS_CNT_INSERTED];
+    c->t_used += inserted;
+    c->t_live += inserted;
+    // CLB:121-125 for every placed item, duplicates included; an item without an invoker never reaches them
+    c->f_total += placed;
+    c->f_mb_managed += (long long)H[OWGS_PUB_CNT + OWGS_CNT_MANAGED_MB];
+    c->f_mb_blackbox += (long long)H[OWGS_PUB_CNT + OWGS_CNT_BLACKBOX_MB];
+    out_summary[0] = placed;
+    out_summary[1] = inserted;
+    out_summary[2] = (int64_t)H[OWGS_PUB_OVL_MANAGED];
+    out_summary[3] = (int64_t)H[OWGS_PUB_OVL_BLACKBOX];
+    out_summary[4] = (int64_t)H[OWGS_PUB_NONE];
+    out_summary[5] = (int64_t)H[OWGS_PUB_THROW];
+    out_summary[6] = 2;
+    for (int32_t i = 0; i < n; ++i)
+        if (out_existed[i] == 2) return c->fail(OWGS_EDEVICE, (std::string(who) + ": activation table full").c_str());
+    if (!msgs) return OWGS_OK;
+    const int32_t mm = (int32_t)H[OWGS_PUB_MSG_M];
+    const int64_t tot = (int64_t)H[OWGS_PUB_MSG_TOTAL];
+    mo->total = tot;
+    mo->m = mm;
+    int rc = msg_verdict(c, (int32_t)H[OWGS_PUB_MSG_BAD]);
+    if (!rc) rc = msg_download(c, mo->n_topics, tot, mm, mo->out, mo->out_off, mo->out_order, mo->topic_start, st);
+    if (rc) return rc;  // the entries stay, left to their timeouts (SCPB:302-303): serialise again with out_invoker
+    out_summary[6] = 3;
+    return OWGS_OK;
+}
+
 // ShardingContainerPoolBalancer.publish (SCPB:257-317) for a drained batch: schedule, setupActivation for the placed
 // items, the serialised messages -- the decisions never leave the device between the stages.  On an
 // on-chip context nothing below waits between queueing the engine and the one block copy; the gate kernel reads the
@@ -5274,42 +5341,263 @@ int owgs_publish_activations(owgs_ctx* c, const owgs_publish_io* io, const owgs_
     }
     HIPCHK(c, hipMemcpyAsync(c->p_pin, c->p_blk.p, blk_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    const unsigned long long* H = (const unsigned long long*)c->p_pin;
-    if (H[OWGS_PUB_ERR]) {  // the engine failed: the gate placed nothing, the table and the books are untouched
-        rc = check_err_word(c);
-        return rc ? rc : c->fail(OWGS_EDEVICE, "publish: the engine's error word was set");
-    }
     const char* P = (const char*)c->p_pin + hdr_bytes;
-    memcpy(io->out_invoker, P, (size_t)n * 4);
-    memcpy(io->out_ticket, P + (size_t)n * 4, (size_t)n * 4);
-    memcpy(io->out_flags, P + (size_t)n * 8, (size_t)n);
-    memcpy(io->out_existed, P + (size_t)n * 9, (size_t)n);
-    const long long placed = (long long)H[OWGS_PUB_PLACED], inserted = (long long)H[OWGS_PUB_CNT + OWGS_CNT_INSERTED];
-    c->t_used += inserted;
-    c->t_live += inserted;
-    // CLB:121-125 for every placed item, duplicates included; an item without an invoker never reaches them
-    c->f_total += placed;
-    c->f_mb_managed += (long long)H[OWGS_PUB_CNT + OWGS_CNT_MANAGED_MB];
-    c->f_mb_blackbox += (long long)H[OWGS_PUB_CNT + OWGS_CNT_BLACKBOX_MB];
-    out_summary[0] = placed;
-    out_summary[1] = inserted;
-    out_summary[2] = (int64_t)H[OWGS_PUB_OVL_MANAGED];
-    out_summary[3] = (int64_t)H[OWGS_PUB_OVL_BLACKBOX];
-    out_summary[4] = (int64_t)H[OWGS_PUB_NONE];
-    out_summary[5] = (int64_t)H[OWGS_PUB_THROW];
-    out_summary[6] = 2;
+    const PublishBlock B{P, P + (size_t)n * 4, P + (size_t)n * 8, P + (size_t)n * 9};
+    return publish_tail(c, "publish", n, B, io->out_invoker, io->out_flags, io->out_ticket, io->out_existed, msgs, mo,
+                        out_summary, st);
+}
+
+// ------------------------------------------------------------------------------------------ gated publish
+// The engine step of owgs_invoke_activations on an on-chip context: publish_device without its uploads.  The admitted
+// actions are in d_a (and d_seq) and their count m only on the device, as the batch offsets {0, m} in d_off; n bounds
+// it.  Checked against m on the device: the pre-pass and the engine take every bound from d_off, the
+// host count sizes buffers (d_rec, d_lix, the pre-pass grid, the overflow's upper bound) and clamps the I/O wave's
+// record prefetch; the watch update runs over n items, of which those from m on are padding it returns on.
+static int invoke_engine(owgs_ctx* c, int32_t n, bool has_seq, uint64_t seq_base) {
+    OwgsEngineArgs A;
+    base_args(c, A);
+    A.seq_base = seq_base;
+    A.seq = has_seq ? c->d_seq.p : nullptr;
+    A.out_inv = c->d_out.p;
+    A.out_flags = c->d_flags.p;
+    int rc = run_prepass(c, A, 1, c->d_off.p, c->d_a.p, n, c->stream);
+    if (!rc) rc = run_engine(c, A, c->stream);
+    if (!rc) rc = w_update(c, n, c->d_a.p, c->d_out.p, c->d_flags.p, c->stream);
+    return rc;
+}
+
+// EntitlementProvider.checkThrottles (Entitlement.scala:197-202, 354-381) and, for what it admits,
+// ShardingContainerPoolBalancer.publish (SCPB:257-317) for a drained batch (the semantics are in
+// include/owgs.h).  On an on-chip context nothing below waits between queueing the gate and the one block copy.
+int owgs_invoke_activations(owgs_ctx* c, const owgs_invoke_io* io, const owgs_msg_batch* msgs, owgs_msg_out* mo,
+                            int64_t out_summary[16]) {
+    if (!c || !io || !out_summary) return OWGS_EINVAL;
+    const int32_t n = io->n;
+    if (n < 0 || (msgs == nullptr) != (mo == nullptr)) return OWGS_EINVAL;
+    if (n > 0 && (!io->ns || !io->kind || !io->t_ms || !io->action || !io->aid || !io->ticket || !io->time_limit_ms ||
+                  !io->out_verdict || !io->out_rate_count || !io->out_rate_limit || !io->out_conc_count ||
+                  !io->out_conc_limit || !io->out_invoker || !io->out_flags || !io->out_ticket || !io->out_existed))
+        return OWGS_EINVAL;
+    // the gate's argument contract (owgs_admit_batch)
+    for (int32_t i = 0; i < n; ++i) {
+        const uint8_t kd = io->kind[i];
+        if (io->ns[i] == OWGS_NONE) return c->fail(OWGS_EINVAL, "throttle gate without a namespace");
+        if (kd & ~(OWGS_ADMIT_TRIGGER | OWGS_ADMIT_RATE_OVERRIDE | OWGS_ADMIT_CONC_OVERRIDE))
+            return c->fail(OWGS_EINVAL, "throttle gate: reserved kind bits");
+        if (((kd & OWGS_ADMIT_RATE_OVERRIDE) && !io->rate_override) ||
+            ((kd & OWGS_ADMIT_CONC_OVERRIDE) && !io->conc_override))
+            return c->fail(OWGS_EINVAL, "throttle gate: an override bit without its array");
+        if (io->t_ms[i] < 0 || io->t_ms[i] >= (1LL << 60))
+            return c->fail(OWGS_EINVAL, "throttle gate: time outside [0, 2^60)");
+    }
+    // ... and publish's (owgs_publish_activations), over the items that are actions
+    MsgNeeds need;
+    if (msgs) {
+        if (msgs->n != n) return c->fail(OWGS_EINVAL, "invoke: msgs->n differs from io->n");
+        const int rm = msg_host_check(c, msgs, mo->n_topics, mo->out, mo->cap, mo->out_off, mo->out_order,
+                                      mo->topic_start, true, need);
+        if (rm) return rm;
+    }
+    if (io->now_ms < 0 || io->now_ms >= (1LL << 60)) return c->fail(OWGS_EINVAL, "invoke: now outside [0, 2^60)");
     for (int32_t i = 0; i < n; ++i)
-        if (io->out_existed[i] == 2) return c->fail(OWGS_EDEVICE, "publish: activation table full");
-    if (!msgs) return OWGS_OK;
-    const int32_t mm = (int32_t)H[OWGS_PUB_MSG_M];
-    const int64_t tot = (int64_t)H[OWGS_PUB_MSG_TOTAL];
-    mo->total = tot;
-    mo->m = mm;
-    rc = msg_verdict(c, (int32_t)H[OWGS_PUB_MSG_BAD]);
-    if (!rc) rc = msg_download(c, mo->n_topics, tot, mm, mo->out, mo->out_off, mo->out_order, mo->topic_start, st);
-    if (rc) return rc;  // the entries stay, left to their timeouts (SCPB:302-303): serialise again with out_invoker
-    out_summary[6] = 3;
-    return OWGS_OK;
+        if (!(io->kind[i] & OWGS_ADMIT_TRIGGER) && (io->time_limit_ms[i] < 0 || io->time_limit_ms[i] >= (1LL << 40)))
+            return c->fail(OWGS_EINVAL, "invoke: time limit outside [0, 2^40)");
+    for (int32_t i = 0; i < n; ++i)
+        if (!(io->kind[i] & OWGS_ADMIT_TRIGGER) && !registered(c, 1, io->action + i))
+            return c->fail(OWGS_ENOENT, "unknown action");
+    if (!ns_known(c, n, io->ns)) return c->fail(OWGS_ENOENT, "unknown namespace");
+    for (int k = 0; k < 16; ++k) out_summary[k] = 0;
+    if (n == 0) {
+        if (mo) {
+            mo->total = 0;
+            mo->m = 0;
+            mo->out_off[0] = 0;
+            for (int32_t k = 0; k <= mo->n_topics; ++k) mo->topic_start[k] = 0;
+            out_summary[6] = 3;
+        } else {
+            out_summary[6] = 2;
+        }
+        return OWGS_OK;
+    }
+    OWGS_ENTER(c);
+    {
+        const int ro_ = order_on(c, c->stream);
+        if (ro_) return ro_;
+    }
+    hipStream_t st = c->stream;
+    const size_t N = (size_t)n;
+    // everything that may wait comes first: the table's rehash, the templates, the buffers
+    int rc = act_reserve(c, n);
+    if (!rc && msgs) rc = msg_templates_upload(c, st);
+    if (rc) return rc;
+    const size_t hdr_bytes = (size_t)OWGS_PUB_HDR * 8, blk_bytes = hdr_bytes + N * 27;
+    if (c->p_pin_bytes < blk_bytes) {
+        if (c->p_pin) (void)hipHostFree(c->p_pin);
+        c->p_pin = nullptr;
+        c->p_pin_bytes = 0;
+        HIPCHK(c, hipHostMalloc(&c->p_pin, blk_bytes * 2, hipHostMallocDefault));
+        c->p_pin_bytes = blk_bytes * 2;
+    }
+    HIPCHK(c, c->p_blk.reserve(blk_bytes));
+    HIPCHK(c, c->p_placed.reserve(N));
+    if (msgs) HIPCHK(c, c->p_minv.reserve(N));
+    int32_t bits = 1;
+    while (((int64_t)1 << bits) < (int64_t)c->ns_map.size()) ++bits;
+    const size_t tb = owgs_throttle_sort_bytes(n, bits);
+    HIPCHK(c, c->q_temp.reserve(tb));
+    HIPCHK(c, c->q_key.reserve(N));
+    HIPCHK(c, c->q_idx0.reserve(N));
+    HIPCHK(c, c->q_idx1.reserve(N));
+    HIPCHK(c, c->v_rank.reserve(N));
+    HIPCHK(c, c->d_out.reserve(N));
+    HIPCHK(c, c->d_flags.reserve(N));
+    // the block: header, then the gate's four int32 arrays, out_invoker, out_ticket, then the three byte arrays
+    unsigned long long* hdr = (unsigned long long*)c->p_blk.p;
+    int32_t* b_rc = (int32_t*)(c->p_blk.p + hdr_bytes);
+    int32_t *b_rl = b_rc + N, *b_cc = b_rc + 2 * N, *b_cl = b_rc + 3 * N, *b_inv = b_rc + 4 * N, *b_tick = b_rc + 5 * N;
+    uint8_t *b_ver = (uint8_t*)(b_rc + 6 * N), *b_flags = b_ver + N, *b_ex = b_ver + 2 * N;
+    HIPCHK(c, hipMemsetAsync(hdr, 0, hdr_bytes, st));
+    // stage 0: the gate (owgs_admit_batch), its outputs written into the block
+    HIPCHK(c, upload(c->k_act, io->ns, N, st));
+    HIPCHK(c, upload(c->k_kind, io->kind, N, st));
+    HIPCHK(c, upload(c->k_off, io->t_ms, N, st));
+    if (io->rate_override) HIPCHK(c, upload(c->v_ov0, io->rate_override, N, st));
+    if (io->conc_override) HIPCHK(c, upload(c->v_ov1, io->conc_override, N, st));
+    OwgsAdmitArgs G = admit_args(c, n);
+    G.kind = c->k_kind.p;
+    G.t_ms = c->k_off.p;
+    G.rate_ov = io->rate_override ? c->v_ov0.p : nullptr;
+    G.conc_ov = io->conc_override ? c->v_ov1.p : nullptr;
+    G.out_verdict = b_ver;
+    G.out_rate_count = b_rc;
+    G.out_rate_limit = b_rl;
+    G.out_conc_count = b_cc;
+    G.out_conc_limit = b_cl;
+    HIPCHK(c, owgs_launch_admit(c->k_act.p, bits, c->q_temp.p, tb, c->q_key.p, c->q_idx0.p, c->q_idx1.p, &G, st));
+    int64_t waits = 0;
+    // the five gate outputs from the pinned block (valid whenever the gate ran, whatever happens after it)
+    auto gate_out = [&]() {
+        const char* P = (const char*)c->p_pin + hdr_bytes;
+        memcpy(io->out_rate_count, P, 4 * N);
+        memcpy(io->out_rate_limit, P + 4 * N, 4 * N);
+        memcpy(io->out_conc_count, P + 8 * N, 4 * N);
+        memcpy(io->out_conc_limit, P + 12 * N, 4 * N);
+        memcpy(io->out_verdict, P + 24 * N, N);
+        for (int32_t i = 0; i < n; ++i) {
+            const bool trig = (io->kind[i] & OWGS_ADMIT_TRIGGER) != 0;
+            const uint8_t v = io->out_verdict[i];
+            out_summary[8] += !trig && v == OWGS_ADMIT_OK;
+            out_summary[9] += v == OWGS_ADMIT_RATE;
+            out_summary[10] += v == OWGS_ADMIT_CONCURRENT;
+            out_summary[11] += trig && v == OWGS_ADMIT_OK;
+        }
+    };
+    // the engine step failed on the host side or reported its own error: the rate records stay charged and the gate's
+    // outputs are handed out (the reference charges the rate before publish can fail); nothing is tracked or written
+    auto engine_failed = [&](int code) {
+        if (hipMemcpyAsync(c->p_pin, c->p_blk.p, blk_bytes, hipMemcpyDeviceToHost, st) == hipSuccess &&
+            hipStreamSynchronize(st) == hipSuccess) {
+            gate_out();
+            out_summary[12] = waits + 1;
+        }
+        return code;
+    };
+    // stage 1: the admitted actions through the engine, the decisions left in d_out / d_flags by rank
+    if (c->large) {
+        // the large-state engine's run takes host arrays: the verdicts come back once before it
+        std::vector<uint8_t> ver(N);
+        HIPCHK(c, hipMemcpyAsync(ver.data(), b_ver, N, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        ++waits;
+        std::vector<int32_t> rank(N), act_c;
+        std::vector<uint64_t> seq_c;
+        for (int32_t i = 0; i < n; ++i) {
+            const bool adm = !(io->kind[i] & OWGS_ADMIT_TRIGGER) && ver[i] == OWGS_ADMIT_OK;
+            rank[i] = adm ? (int32_t)act_c.size() : -1;
+            if (adm) {
+                act_c.push_back(io->action[i]);
+                if (io->seq) seq_c.push_back(io->seq[i]);
+            }
+        }
+        HIPCHK(c, upload(c->v_rank, rank.data(), N, st));
+        if (!act_c.empty())
+            rc = publish_device(c, (int32_t)act_c.size(), act_c.data(), io->seq ? seq_c.data() : nullptr, io->seq_base,
+                                nullptr, nullptr);
+        if (rc) return engine_failed(rc);
+    } else {
+        HIPCHK(c, c->d_off.reserve(2));
+        HIPCHK(c, c->d_a.reserve(N));
+        if (io->seq) HIPCHK(c, c->d_seq.reserve(N));
+        HIPCHK(c, c->v_map.reserve(N));
+        HIPCHK(c, c->v_bcnt.reserve((N + 255) / 256));
+        HIPCHK(c, upload(c->v_act, io->action, N, st));
+        if (io->seq) HIPCHK(c, upload(c->v_seq, (const u64*)io->seq, N, st));
+        OwgsInvokeCompact K{};
+        K.n = n;
+        K.verdict = b_ver;
+        K.kind = c->k_kind.p;
+        K.action = c->v_act.p;
+        K.seq = io->seq ? c->v_seq.p : nullptr;
+        K.bcnt = c->v_bcnt.p;
+        K.act_c = c->d_a.p;
+        K.seq_c = io->seq ? c->d_seq.p : nullptr;
+        K.map = c->v_map.p;
+        K.rank = c->v_rank.p;
+        K.off = c->d_off.p;
+        K.pad_out = c->d_out.p;
+        K.pad_flags = c->d_flags.p;
+        HIPCHK(c, owgs_launch_invoke_compact(&K, st));
+        rc = invoke_engine(c, n, io->seq != nullptr, io->seq_base);
+        if (rc) return engine_failed(rc);
+    }
+    // the inputs of stages 2 and 3 go up while the engine runs
+    if (c->large) HIPCHK(c, upload(c->v_act, io->action, N, st));
+    HIPCHK(c, upload(c->k_key, (const ulonglong2*)io->aid, N, st));
+    HIPCHK(c, upload(c->k_r0, io->ticket, N, st));
+    HIPCHK(c, upload(c->x_tl, (const long long*)io->time_limit_ms, N, st));
+    OwgsMsgArgs A{};
+    if (msgs) {
+        rc = msg_upload(c, msgs, need, mo->n_topics, mo->cap, A, st);
+        if (rc) return rc;
+    }
+    OwgsInvokeGate Q{};
+    Q.n = n;
+    Q.err = c->d_err.p;
+    Q.rank = c->v_rank.p;
+    Q.dec = c->d_out.p;
+    Q.dflags = c->d_flags.p;
+    Q.action = c->v_act.p;
+    Q.act_bb = c->d_act_bb.p;
+    Q.placed = c->p_placed.p;
+    Q.msg_inv = msgs ? c->p_minv.p : nullptr;
+    Q.hdr = hdr;
+    Q.out_inv = b_inv;
+    Q.out_ticket = b_tick;
+    Q.out_flags = b_flags;
+    Q.out_existed = b_ex;
+    HIPCHK(c, owgs_launch_invoke_gate(&Q, st));
+    // stage 2: setupActivation of the placed items, by item: the entry's invoker from the scattered decisions, the
+    // namespace the gate's
+    rc = track_device(c, n, c->k_key.p, c->v_act.p, c->k_act.p, c->k_r0.p, b_inv, c->x_tl.p, io->now_ms,
+                      c->p_placed.p, b_tick, b_ex, hdr + OWGS_PUB_CNT, st);
+    if (rc) return rc;
+    // stage 3: the messages of the placed items
+    if (msgs) {
+        A.invoker = c->p_minv.p;
+        A.aid = c->k_key.p;
+        rc = msg_queue(c, A, mo->n_topics, st);
+        if (rc) return rc;
+        HIPCHK(c, owgs_launch_publish_collect(hdr, c->m_bad.p, A.topic_start, mo->n_topics, A.out_off, n, st));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->p_pin, c->p_blk.p, blk_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    ++waits;
+    gate_out();
+    out_summary[12] = waits;
+    const char* P = (const char*)c->p_pin + hdr_bytes;
+    const PublishBlock B{P + 16 * N, P + 20 * N, P + 25 * N, P + 26 * N};
+    return publish_tail(c, "invoke", n, B, io->out_invoker, io->out_flags, io->out_ticket, io->out_existed, msgs, mo,
+                        out_summary, st);
 }
 
 int owgs_resident_stats(owgs_ctx* c, int64_t* out, int32_t cap) {

@@ -680,6 +680,44 @@ struct OwgsPublishGate {
     uint8_t* out_existed;
 };
 
+// owgs_invoke_activations (owgs_invoke.hip): the throttle gate feeds the engine on the device.  The admitted actions
+// (kind bit 0 clear, verdict OWGS_ADMIT_OK) are compacted in array order into the engine's input; the engine and the
+// pre-pass read their bounds {0, m} from `off`, the host only knows the upper bound n.  The call's outputs leave the
+// device as ONE block: OWGS_PUB_HDR header words (as above), then rate_count, rate_limit, conc_count, conc_limit,
+// out_invoker, out_ticket [n] (int32), then verdict, out_flags, out_existed [n] (bytes).
+#define OWGS_NOT_PUBLISHED_V (-3)
+struct OwgsInvokeCompact {
+    int32_t n;
+    const uint8_t* verdict;      // [n] the gate's verdicts
+    const uint8_t* kind;         // [n] bit0: a trigger
+    const int32_t* action;       // [n] by item; read only for admitted actions
+    const unsigned long long* seq;  // [n] by item, or null (the engine then counts seq_base + k itself)
+    int32_t* bcnt;               // [ceil(n / 256)] admitted actions per block of 256 items (count kernel -> scatter)
+    int32_t* act_c;              // out [n]: action of the k-th admitted action; handle 0 from m on (see pad_out)
+    unsigned long long* seq_c;   // out [n] (with seq): seq of the k-th admitted action
+    int32_t* map;                // out [n]: k -> item, valid below m
+    int32_t* rank;               // out [n]: item -> k, or -1
+    int64_t* off;                // out [2]: {0, m}, the engine's batch offsets
+    int32_t* pad_out;            // the engine's decision arrays: entries [m, n) become (OWGS_NONE, 0), which with a valid
+    uint8_t* pad_flags;          // handle is what owgs_w_depth_kernel returns on without a write
+};
+struct OwgsInvokeGate {
+    int32_t n;
+    const int32_t* err;          // as OwgsPublishGate
+    const int32_t* rank;         // [n] item -> position among the admitted actions, or -1
+    const int32_t* dec;          // [m] the engine's decisions, by that position
+    const uint8_t* dflags;
+    const int32_t* action;       // [n] by item; read only for placed items
+    const uint8_t* act_bb;
+    uint8_t* placed;             // out [n], by item
+    int32_t* msg_inv;            // out [n] or null
+    unsigned long long* hdr;
+    int32_t* out_inv;            // block arrays, by item: OWGS_NOT_PUBLISHED / 0 / -1 / 0 for an item that is not an
+    int32_t* out_ticket;         // admitted action
+    uint8_t* out_flags;
+    uint8_t* out_existed;
+};
+
 struct OwgsAckCompleteArgs {
     const ulonglong2* key;
     const uint8_t* info;
