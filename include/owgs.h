@@ -805,6 +805,11 @@ int owgs_invoke_activations(owgs_ctx* ctx, const owgs_invoke_io* io, const owgs_
  * waits for it to finish.  Measurement hook for bench.py's roofline. */
 int owgs_engine_ms(owgs_ctx* ctx, float* ms);
 
+/* Diagnostics (leak tests): what the library holds in this process, over every context: out[0] device allocations,
+ * [1] pinned host blocks, [2] events and streams it created.  All three are back at their earlier values once the
+ * contexts created since have been destroyed.  No device work; needs no context. */
+int owgs_live_resources(int64_t out[3]);
+
 /* Counters of owgs_process_batch's two paths: out[0] calls the resident engine served, [1] its launches, [2] calls it
  * refused untouched (a release that could leave the on-chip permit range; the chain took them), [3] calls the launch
  * chain took, [4] 1 while a resident engine is live; then, summed over the served calls: [5] walk rounds, [6]

@@ -138,6 +138,7 @@ def lib() -> C.CDLL:
         "owgs_health_events": (C.c_int, [P, i32, P, P, P, P, C.c_int64, i32]),
         "owgs_register_templates": (C.c_int, [P, i32, P, P, P, P, P]),
         "owgs_engine_ms": (C.c_int, [P, P]),
+        "owgs_live_resources": (C.c_int, [P]),
         "owgs_resident_stats": (C.c_int, [P, P, i32]),
         "owgs_large_stats": (C.c_int, [P, P, i32]),
         "owgs_set_root_controller": (C.c_int, [P, C.c_char_p, i32]),
@@ -202,3 +203,12 @@ def lib() -> C.CDLL:
         fn.argtypes = args
     _lib = L
     return L
+
+
+def live_resources() -> tuple[int, int, int]:
+    """What the library holds in this process: (device allocations, pinned host blocks, events + streams)."""
+    out = (C.c_int64 * 3)()
+    rc = lib().owgs_live_resources(out)
+    if rc < 0:
+        raise OwgsError(rc, "owgs_live_resources")
+    return out[0], out[1], out[2]

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "owgs_internal.h"
+#include "owgs_launch.h"
 
 typedef unsigned long long u64;
 

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "owgs_internal.h"
+#include "owgs_launch.h"
 
 #define EV_PING 0
 #define EV_SUCCESS 1

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "owgs_internal.h"
+#include "owgs_launch.h"
 
 // one workgroup per run: class counts, then stable placement by ballot ranks
 __global__ __launch_bounds__(256) void owgs_stage_releases_kernel(OwgsStageArgs a) {

@@ -28,6 +28,8 @@
 
 #include <stdint.h>
 
+#include "owgs_launch.h"
+
 #define H_HEALTHY 0
 #define H_UNHEALTHY 1
 #define H_UNRESPONSIVE 2

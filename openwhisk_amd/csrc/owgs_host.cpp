@@ -1,512 +1,17 @@
-// owgs_host.cpp -- host runtime behind include/owgs.h.
+// owgs_host.cpp -- host runtime behind include/owgs.h (the context itself: owgs_ctx.h; the completion path and the
+// message output: owgs_host_acks.cpp, owgs_host_msgs.cpp).
 //
 // Holds the controller-shard structure that changes rarely (invoker list, managed/blackbox split, step sizes,
 // cluster size) and mirrors ShardingContainerPoolBalancerState (SCPB:449-585) line by line; everything touched per
 // activation (slot permits, concurrency maps, outputs) lives in HBM and is updated by the HIP engine
 // (owgs_kernels.hip).  No CPU fallback exists: without a HIP device every compute entry point fails.
-#include <hip/hip_runtime.h>
+#include "owgs_ctx.h"
 
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdlib>
-#include <cstdio>
-#include <cstring>
-#include <map>
-#include <string>
-#include <unordered_map>
-#include <vector>
-
-#include "../../include/owgs.h"
-#include "owgs_internal.h"
-
-typedef unsigned long long u64;
-
-extern "C" hipError_t owgs_launch_hash(const OwgsHashArgs* a, hipStream_t s);
-extern "C" hipError_t owgs_launch_lookup(const OwgsLookupArgs* a, hipStream_t s);
-extern "C" hipError_t owgs_launch_selftest(int* bad, int trials, hipStream_t s);
-extern "C" hipError_t owgs_launch_prepare(const OwgsPrepArgs* a, hipStream_t s);
-extern "C" hipError_t owgs_launch_prepass(const OwgsPrepassArgs* a, int32_t* cstart, int64_t max_chunks,
-                                          hipStream_t s);
-extern "C" hipError_t owgs_launch_ovf_clear(const OwgsOvf* O, hipStream_t s);
-extern "C" hipError_t owgs_launch_ovf_rehash(const uint2* old_t, int32_t old_cap, const OwgsOvf* O, int32_t* err,
-                                            hipStream_t s);
-extern "C" hipError_t owgs_launch_relpos(const OwgsRelposArgs* a, hipStream_t s);
-extern "C" hipError_t owgs_launch_relflags(const int64_t* rel_aid, int64_t n_rel, const int32_t* out_inv,
-                                           uint8_t* rel_flags, hipStream_t s);
-extern "C" hipError_t owgs_launch_release_seq(const OwgsReleaseArgs* a, hipStream_t s);
-extern "C" size_t owgs_release_scratch_bytes(int32_t n);
-extern "C" hipError_t owgs_launch_engine(const OwgsEngineArgs* a, hipStream_t s);
-extern "C" hipError_t owgs_launch_engine_multi(const OwgsEngineArgs* a, int k, hipStream_t s);
-extern "C" hipError_t owgs_launch_engine_multi_dev(const OwgsEngineArgs* a_host, const OwgsEngineArgs* a_dev, int k,
-                                                   hipStream_t s);
-extern "C" int32_t owgs_coprime_max(void);
-extern "C" hipError_t owgs_launch_coprime(const int32_t* xs, int32_t n_pools, int32_t* out, int32_t out_stride,
-                                          int32_t* counts, hipStream_t s);
-extern "C" hipError_t owgs_launch_slots(const int64_t* mem_bytes, int32_t from, int32_t n, int32_t cluster,
-                                       int64_t min_bytes, int32_t* permits, hipStream_t s);
-extern "C" hipError_t owgs_launch_seq(const OwgsSeqArgs* a, hipStream_t s);
-extern "C" hipError_t owgs_launch_seq_rehash(const uint4* old, int32_t old_cap, const OwgsSeqArgs* a, hipStream_t s);
-extern "C" hipError_t owgs_launch_seq_migrate(const uint32_t* ct_keys, const uint32_t* ct_vals, int32_t n_ct,
-                                              const uint2* ovf, int32_t ovf_cap, const uint32_t* w_keys,
-                                              const uint32_t* w_vals, int32_t w_cap, const OwgsSeqArgs* a, hipStream_t s);
-extern "C" hipError_t owgs_launch_seq_lookup(const OwgsSeqArgs* a, int32_t inv, int32_t slot, int32_t* out, hipStream_t s);
-extern "C" hipError_t owgs_launch_usable_rows(const uint8_t* status, int64_t stride, int32_t n, int32_t rows,
-                                              uint32_t* bits, int32_t n_words, hipStream_t s);
-extern "C" hipError_t owgs_launch_usable(const uint8_t* status, int32_t n, uint32_t* bits, int32_t n_words,
-                                        hipStream_t s);
-extern "C" hipError_t owgs_launch_slot_scan(const uint32_t* ct_keys, const uint2* ovf, int32_t ovf_cap,
-                                           const uint32_t* w_keys, int32_t w_cap, const int32_t* wkey, uint32_t* cand,
-                                           hipStream_t s);
-extern "C" hipError_t owgs_launch_ack_parse(const OwgsAckParseArgs* a, hipStream_t st);
-extern "C" hipError_t owgs_launch_aid_decode(const char* aid32, int32_t n, const uint8_t* cflags, ulonglong2* key,
-                                             uint8_t* info, int32_t* inst, const int32_t* inv, hipStream_t st);
-extern "C" hipError_t owgs_launch_act_init(const OwgsActTable* T, hipStream_t st);
-extern "C" hipError_t owgs_launch_act_rehash(const OwgsActTable* O, const OwgsActTable* T, hipStream_t st);
-extern "C" hipError_t owgs_launch_act_track(const OwgsActTable* T, const ulonglong2* key, int32_t n,
-                                            const int32_t* action, const int32_t* ns, const int32_t* ticket,
-                                            int32_t* slot, uint8_t* state, int32_t* out_ticket, uint8_t* out_existed,
-                                            unsigned long long* counters, const OwgsInflight* F, const OwgsArm* arm,
-                                            const uint8_t* placed, hipStream_t st);
-extern "C" hipError_t owgs_launch_publish_gate(const OwgsPublishGate* g, hipStream_t st);
-extern "C" hipError_t owgs_launch_publish_collect(unsigned long long* hdr, const int32_t* bad,
-                                                  const int32_t* topic_start, int32_t n_topics,
-                                                  const int64_t* out_off, int32_t n, hipStream_t st);
-extern "C" hipError_t owgs_launch_expire_scan(const OwgsExpireArgs* a, hipStream_t st);
-extern "C" size_t owgs_expire_sort_bytes(int32_t n);
-extern "C" hipError_t owgs_launch_expire_order(const OwgsExpireArgs* a, int32_t n, int32_t take, int32_t seq_bits,
-                                               void* temp, size_t temp_bytes, int32_t* idx0, int32_t* idx1,
-                                               unsigned long long* key, unsigned long long* key_s, ulonglong2* key_out,
-                                               int32_t* inst, uint8_t* info, long long* out_deadline, hipStream_t st);
-extern "C" hipError_t owgs_launch_deadline_min(const OwgsActTable* T, long long* out, hipStream_t st);
-extern "C" hipError_t owgs_launch_ns_gather(const int32_t* active, const int32_t* ns, int32_t n, int32_t* out,
-                                            hipStream_t st);
-extern "C" size_t owgs_throttle_sort_bytes(int32_t n, int32_t bits);
-extern "C" hipError_t owgs_launch_throttle(const int32_t* ns, const int32_t* limit, int32_t n, int32_t bits,
-                                           void* temp, size_t temp_bytes, int32_t* key_out, int32_t* idx_in,
-                                           int32_t* idx_out, const int32_t* active, int32_t* out_count,
-                                           uint8_t* out_ok, hipStream_t st);
-extern "C" hipError_t owgs_launch_admit(const int32_t* ns, int32_t bits, void* temp, size_t temp_bytes,
-                                        int32_t* key_out, int32_t* idx_in, int32_t* idx_out, const OwgsAdmitArgs* args,
-                                        hipStream_t st);
-extern "C" hipError_t owgs_launch_rate_gather(const long long* rate_min, const int32_t* rate_cnt, int32_t ns_cap,
-                                              int32_t which, const int32_t* ns, int32_t n, long long* out_min,
-                                              int32_t* out_cnt, hipStream_t st);
-extern "C" hipError_t owgs_launch_rate_grow(const long long* old_min, const int32_t* old_cnt, int32_t old_cap,
-                                            long long* new_min, int32_t* new_cnt, int32_t new_cap, hipStream_t st);
-extern "C" hipError_t owgs_launch_ack_complete(const OwgsActTable* T, const OwgsAckCompleteArgs* a, hipStream_t st);
-extern "C" hipError_t owgs_launch_ack_flags(int32_t n, const uint8_t* info, const uint8_t* rflags,
-                                            const uint8_t* out_kind, uint8_t* out_flags, const ulonglong2* key,
-                                            unsigned long long* out_aid, hipStream_t st);
-extern "C" hipError_t owgs_launch_ack_parse_results(const OwgsAckParseResultArgs* a, hipStream_t st);
-extern "C" hipError_t owgs_launch_health_init(uint8_t* s, uint32_t* ring, int64_t* last, int64_t* tick, int64_t* mem,
-                                              int32_t* tests, int32_t from, int32_t to, hipStream_t st);
-extern "C" size_t owgs_health_sort_bytes(int32_t n, int32_t bits);
-extern "C" hipError_t owgs_launch_health_batch(const int32_t* ev_inv, const uint8_t* ev_kind, const int64_t* ev_t,
-                                               const int64_t* ev_mem, int32_t n, int32_t bits, void* temp,
-                                               size_t temp_bytes, int32_t* key_out, int32_t* idx_in,
-                                               int32_t* idx_out, int64_t* packed, int32_t* seg_beg, int32_t* seg_end,
-                                               int32_t* reg_first, int32_t* pad_src, uint8_t* s, uint32_t* ring,
-                                               int64_t* last, int64_t* tick, int64_t* mem, int32_t* tests,
-                                               int32_t old_size, int32_t new_size, int64_t now, int32_t* sum,
-                                               hipStream_t st);
-extern "C" hipError_t owgs_launch_ping_parse(const uint8_t* bytes, const int64_t* off, int32_t n, uint8_t* out_kind,
-                                             int32_t* out_inst, long long* out_mem, hipStream_t st);
-extern "C" hipError_t owgs_launch_feed_compact(const OwgsFeedArgs* a, int mode, hipStream_t st);
-extern "C" size_t owgs_msg_scratch_bytes(int32_t n, int32_t n_topics, int32_t bits);
-extern "C" hipError_t owgs_launch_msg_plan(const OwgsMsgArgs* a, int32_t bits, void* temp, size_t temp_bytes,
-                                           uint32_t* key_sorted, int32_t* iota, int64_t* len_sorted, int32_t* cnt,
-                                           hipStream_t st);
-extern "C" hipError_t owgs_launch_msg_write(const OwgsMsgArgs* a, hipStream_t st);
-extern "C" size_t owgs_engine_lds_bytes(int n_slots, int pool_mode, int n_ids, int nm, int nb, int n_actions);
-// the narrow geometry (owgs_engine_narrow.hip): same ABI, 7 x 32-lane chunks
-extern "C" size_t owgs_engine_lds_bytes_narrow(int n_slots, int pool_mode, int n_ids, int nm, int nb, int n_actions);
-extern "C" hipError_t owgs_launch_prepass_narrow(const OwgsPrepassArgs* a, int32_t* cstart, int64_t max_chunks,
-                                                 hipStream_t s);
-extern "C" hipError_t owgs_launch_engine_narrow(const OwgsEngineArgs* a, hipStream_t s);
-extern "C" hipError_t owgs_launch_engine_multi_narrow(const OwgsEngineArgs* a, int k, hipStream_t s);
-extern "C" hipError_t owgs_launch_engine_multi_dev_narrow(const OwgsEngineArgs* a_host, const OwgsEngineArgs* a_dev,
-                                                          int k, hipStream_t s);
-#define OWGS_WL_NARROW (OWGS_EW * 32)
-extern "C" hipError_t owgs_launch_w_rebuild(const OwgsWRebuildArgs* a, hipStream_t s);
-extern "C" hipError_t owgs_launch_stage_releases(const OwgsStageArgs* a, hipStream_t s);
-extern "C" hipError_t owgs_launch_relmeta(int32_t n, const int32_t* act, const int32_t* act_mem,
-                                          const int32_t* act_maxc, const int32_t* act_slot, int32_t* mem,
-                                          int32_t* maxc, int32_t* slot, hipStream_t s);
-extern "C" hipError_t owgs_launch_w_update(const OwgsWUpdateArgs* a, hipStream_t s);
-extern "C" hipError_t owgs_launch_invoke_compact(const OwgsInvokeCompact* a, hipStream_t st);
-extern "C" hipError_t owgs_launch_invoke_gate(const OwgsInvokeGate* g, hipStream_t st);
-extern "C" size_t owgs_resident_image_bytes(int32_t n_slots, int32_t n_ids);
-extern "C" hipError_t owgs_launch_resident(const OwgsResArgs* a, size_t lds_bytes, hipStream_t s);
-extern "C" hipError_t owgs_launch_w_relgather(const int64_t* rel_aid, int32_t n, const int32_t* out_inv,
-                                              const int32_t* act, const int32_t* act_mem, const int32_t* act_maxc,
-                                              const int32_t* act_slot, int32_t* inv, int32_t* mem, int32_t* maxc,
-                                              int32_t* slot, hipStream_t s);
-
-namespace {
-
-// diagnostic environment switches, read once per process (not on every call)
-struct EnvOpts {
-    int opts = 0, cw = 0, deal = -1, variant = -1;
-    bool trace = false, feat_all = false;
-    // owgs_process_batch through the resident engine: on/off, the largest call (releases + publishes) it takes, and
-    // its idle time before it writes the state back and exits (OWGS_RESIDENT=0 sends every call down the chain)
-    int res = 1, res_max = 1024;
-    long long res_idle_us = 20000;
-    // ... and its lifetime: it exits between calls once this long after its launch even when busy (it holds a hardware
-    // queue that another context's stream may share; GPU_MAX_HW_QUEUES is 4), the next call relaunches it
-    long long res_life_us = 100000;
-    // watched pairs (after updateCluster) on the resident engine (0: such calls take the launch chain, as in round 4)
-    int res_watch = 1;
-    int res_eager = 1;  // OWGS_RES_EAGER=0: after a chained call the engine is relaunched by the next small call only
-    // (tests) the doorbell's and the walk-cursor generation's values at the context's first launch: start a context
-    // just below their wrap limits
-    long long res_call_base = 0, res_gen_base = 0;
-    // the resident engine's speculative walks: walk steps each publish probes on its own before the in-order
-    // validation (0: every decision walked one at a time)
-    int res_spec = 16;
-    int res_cspec = 0;  // OWGS_RES_CSPEC: walk steps a concurrent publish speculates (0: max(4, res_spec / 4))
-    int res_cspec_pre = 0;  // OWGS_RES_CSPEC_PRE: ... when the helper speculates the next chunk ahead (0: as above)
-    int res_split = 1;  // OWGS_RES_SPLIT: helper waves (0-3) for the concurrent speculation; 0 = wave 0 itself
-    // OWGS_RES_PRE=0: the helper wave does not speculate a run's next chunk while wave 0 decides the current one
-    int res_pre = 1;
-    // owgs_replay_device through the resident engine's stream mode (one wave deciding, speculative walks) instead of
-    // the chunked engine, where it applies (identity pools, no watched pairs)
-    int spec_replay = 0;
-    EnvOpts() {
-        if (const char* e = getenv("OWGS_SPEC_REPLAY")) spec_replay = atoi(e);
-        if (const char* e = getenv("OWGS_RESIDENT")) res = atoi(e);
-        if (const char* e = getenv("OWGS_RES_SPEC")) res_spec = atoi(e);
-        if (const char* e = getenv("OWGS_RES_CSPEC")) res_cspec = atoi(e);
-        if (const char* e = getenv("OWGS_RES_CSPEC_PRE")) res_cspec_pre = atoi(e);
-        if (const char* e = getenv("OWGS_RES_SPLIT")) res_split = atoi(e);
-        if (const char* e = getenv("OWGS_RES_PRE")) res_pre = atoi(e);
-        if (const char* e = getenv("OWGS_RES_MAX")) res_max = atoi(e);
-        if (const char* e = getenv("OWGS_RES_IDLE_US")) res_idle_us = atoll(e);
-        if (const char* e = getenv("OWGS_RES_LIFE_US")) res_life_us = atoll(e);
-        if (const char* e = getenv("OWGS_RES_WATCH")) res_watch = atoi(e);
-        if (const char* e = getenv("OWGS_RES_EAGER")) res_eager = atoi(e);
-        if (const char* e = getenv("OWGS_RES_CALL_BASE")) res_call_base = atoll(e);
-        if (const char* e = getenv("OWGS_RES_GEN_BASE")) res_gen_base = atoll(e);
-        feat_all = getenv("OWGS_FEAT_ALL") != nullptr;  // the general engine for every launch (A/B diagnostics)
-        if (const char* e = getenv("OWGS_VARIANT")) variant = atoi(e);  // force an engine geometry (diagnostics)
-        if (const char* o = getenv("OWGS_OPTS")) opts = atoi(o);
-        if (const char* e = getenv("OWGS_CW")) cw = atoi(e);
-        if (const char* e = getenv("OWGS_DEAL")) deal = atoi(e);
-        trace = getenv("OWGS_TRACE_FILE") != nullptr;
-    }
-};
-const EnvOpts& env_opts() {
-    static const EnvOpts e;
-    return e;
-}
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    hipError_t reserve(size_t m) {
-        if (m <= n && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        size_t bytes = (m ? m : 1) * sizeof(T);
-        hipError_t e = hipMalloc((void**)&p, bytes);
-        if (e == hipSuccess) n = m ? m : 1;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-int32_t d2i(double d) {  // Scala Double.toInt
+static int32_t d2i(double d) {  // Scala Double.toInt
     if (d != d) return 0;
     if (d >= 2147483647.0) return 2147483647;
     if (d <= -2147483648.0) return (-2147483647 - 1);
     return (int32_t)d;
-}
-
-}  // namespace
-struct owgs_ctx {
-    owgs_config cfg{};
-    double mf = 0, bf = 0;
-    std::string err;
-    hipStream_t stream = nullptr;
-
-    // ShardingContainerPoolBalancerState mirror
-    std::vector<int32_t> ids;
-    std::vector<int64_t> mem;
-    std::vector<uint8_t> status;
-    int32_t managed = 0, blackboxes = 0;
-    std::vector<int32_t> msteps, bsteps;
-    int32_t cluster = 1;
-    int32_t n_slots = 0;
-    bool pool_override[2] = {false, false};
-    std::vector<int32_t> ov_ids[2];
-    std::vector<uint8_t> ov_status[2];
-
-    // derived pools
-    int32_t nm = 0, nb = 0, hm = 0, hb = 0, shortcut_ok = 3;
-    int32_t pool_mode = 0, n_ids = 0;  // 0: pool position p -> id p (managed) / N - nb + p (blackbox)
-
-    // actions
-    std::vector<int32_t> a_mem, a_maxc, a_slot, a_hash;
-    std::vector<uint8_t> a_bb, a_cok, a_live;
-    std::vector<int32_t> free_handles;  // released action handles (owgs_release_actions), reused by registrations
-    std::vector<int32_t> slot_uses, slot_maxc, slot_mem;  // per fqn@version key: live handles naming it, its limits
-    std::vector<std::string> slot_name;
-    std::unordered_map<std::string, int32_t> slot_ids;
-    // keys no live handle names: recycled (slot id reused) once no map entry and no watched pair names them any more,
-    // checked on the device when registrations run out of ids (reclaim_slots); slot_epoch counts recycled keys
-    std::vector<int32_t> pending_slots, free_slots;
-    int64_t slot_epoch = 0, snap_slot_epoch = 0;
-    DevBuf<uint32_t> d_cand;
-
-    // device state
-    DevBuf<int32_t> d_permits, d_pool_words, d_hlist, d_act_slot, d_act_hash, d_act_mem, d_act_maxc, d_steps,
-        d_cpx, d_err;
-    // the primary table's entries right after the chunked engine's last rebuild of it, kept across launches (a
-    // launch rebuilds once its entries grew by OWGS_CTC / 8 since then; 0 after a restore: as if never rebuilt)
-    DevBuf<int32_t> d_clast;
-    int32_t steps_stride = 0;  // d_steps = [managed list | blackbox list], each steps_stride entries
-    DevBuf<int64_t> d_mem_bytes;  // userMemory of every invoker (updateCluster recomputes all slots from it)
-    DevBuf<uint8_t> d_status;
-    DevBuf<uint32_t> d_usable, d_ct_keys, d_ct_vals, d_ct_tmp;
-    DevBuf<uint8_t> d_act_bb, d_act_cok;
-    DevBuf<uint2> d_act_meta;
-    DevBuf<u64> d_stats;
-    // NestedSemaphore map overflow (keys beyond the LDS-sized primary table, owgs_internal.h OwgsOvf)
-    DevBuf<uint2> d_ovf, s_ovf;
-    DevBuf<uint32_t> d_ovf_rc;
-    DevBuf<int32_t> d_ovf_touched, d_ovf_cnt;  // d_ovf_cnt = {entries (live + deleted), touched count}
-    int32_t ovf_cap = 0;
-    int64_t ovf_used_ub = 0;  // host upper bound of the overflow's entries (exact after a read-back)
-    // the overflow's entry count copied back after engine launches without waiting (a ring of pinned words +
-    // events): read when the bound above runs out.  A probe that has arrived replaces the bound; otherwise the host
-    // waits for an OLDER probe than the newest -- the launches after it keep the GPU busy meanwhile -- instead of
-    // draining the stream (a batch-by-batch replay then never idles the engine stream on this bound)
-    static constexpr int OVF_PROBES = 4;
-    int32_t* h_ovf_cnt = nullptr;                   // [OVF_PROBES]
-    hipEvent_t ev_ovf[OVF_PROBES] = {};
-    bool ovf_probe[OVF_PROBES] = {};                // slot recorded and not yet consumed
-    int64_t ovf_probe_added[OVF_PROBES] = {};       // ovf_added at the slot's recording (its launch included)
-    int64_t ovf_added = 0;                          // activations ever added to the bound
-    int ovf_probe_next = 0;
-    // owgs_update_health_device on identity pools: the status bytes and usable bitmap are updated on the device only;
-    // the host mirror (status, healthy counts) is downloaded when a host path needs it (ev_status: the copy)
-    bool status_stale = false;
-    hipEvent_t ev_status = nullptr;
-    // calls on one context are ordered as issued, whatever stream each names: ev_tail marks the end of the last
-    // asynchronous call's work (on tail_stream); later work on another stream waits for it (order_on / tail_mark)
-    hipEvent_t ev_tail = nullptr;
-    hipStream_t tail_stream = nullptr;
-    bool tail_valid = false;
-    int32_t s_ovf_cnt = 0;    // snapshot: overflow entries (0: the snapshot had none)
-    int32_t s_ovf_cap = 0;
-    DevBuf<uint32_t> d_margs;  // owgs_replay_device_multi: shard argument blocks beyond the kernarg segment
-    void* h_margs = nullptr;   // pinned staging of d_margs (hipHostMalloc), h_margs_bytes long
-    size_t h_margs_bytes = 0;
-    hipEvent_t ev_margs = nullptr;  // recorded after the last engine launch that reads d_margs / h_margs
-    bool ev_margs_valid = false;
-    // per-call scratch
-    DevBuf<int64_t> d_off;
-    DevBuf<int32_t> d_a, d_b, d_c, d_d, d_out, d_cstart, d_relx, d_relcnt, d_xslot;
-    DevBuf<uint8_t> d_flags, d_rflags;
-    DevBuf<u64> d_seq;
-    DevBuf<int64_t> d_rel;
-    DevBuf<uint4> d_rec;
-    DevBuf<uint32_t> d_lix;
-    DevBuf<uint32_t> d_gcur;  // per-action walk cursors (tagged by batch)
-    DevBuf<unsigned long long> d_trace;  // barrier timeline (diagnostic builds, env OWGS_TRACE_FILE)
-    int32_t cur_tag = 0;      // tags used so far (wraps with a clear of d_gcur)
-    DevBuf<uint2> d_rel_rec, d_xmeta;
-    // activationSlots (owgs_acks.hip)
-    DevBuf<unsigned long long> t_tw;
-    DevBuf<ulonglong2> t_tk;
-    DevBuf<int2> t_tv;
-    DevBuf<int32_t> t_tn, t_owner;
-    long long t_cap = 0, t_used = 0, t_live = 0;
-    // completion-ack timeouts (owgs_expire.hip): per-slot deadline / entry invoker / arm sequence, the per-tile summary,
-    // calculateCompletionAckTimeout's three settings (CLB:103-105), the arm-sequence counter, the sweep's scratch and
-    // its counters (owgs_expiry_stats)
-    DevBuf<long long> t_td, t_tmin, x_d, x_tl, x_outd;
-    DevBuf<int32_t> t_ti, x_slot, x_idx0, x_idx1, x_cnt, x_inv;
-    DevBuf<unsigned long long> t_tq, x_q, x_key, x_key_s;
-    DevBuf<uint8_t> x_temp;
-    long long a_std = 60000, a_factor = 2, a_addon = 60000;
-    unsigned long long arm_seq = 0;
-    long long x_sweeps = 0, x_tiles = 0, x_tiles_last = 0, x_expired = 0;
-    // the in-flight books (CLB:62-65): namespace uuid -> dense handle, the per-namespace counters on the device
-    // (int32, ns_cap entries, zero beyond the registered handles), the three totals on the host (folded in from each
-    // call's counter words at the synchronisation the call ends with)
-    std::map<std::pair<uint64_t, uint64_t>, int32_t> ns_map;
-    DevBuf<int32_t> d_ns_active, q_key, q_idx0, q_idx1;
-    DevBuf<uint8_t> q_temp;
-    int32_t ns_cap = 0;
-    // the entitlement throttle gate (owgs_admit_batch): the RateInfo records of the two rate throttlers, entry
-    // which * ns_cap + handle (lastMin OWGS_RATE_ABSENT, count 0: never checked), grown with d_ns_active; the three
-    // system defaults (Entitlement.scala:138, 142, 153; ansible/group_vars/all:73-75); its output block on the device
-    // ([4 n] int32 then [n] verdict bytes) and the pinned host block it is read back into with one copy
-    DevBuf<long long> d_rate_min, g_min;
-    DevBuf<int32_t> d_rate_cnt, g_out;
-    void* g_pin = nullptr;
-    size_t g_pin_bytes = 0;
-    int32_t lim_invoke = 60, lim_fire = 60, lim_conc = 30;
-    long long f_total = 0, f_mb_managed = 0, f_mb_blackbox = 0;
-    long long health_ms = 0;
-    DevBuf<ulonglong2> k_key;
-    DevBuf<uint8_t> k_info, k_state, k_kind, k_oflags, k_bytes, k_cfl;
-    DevBuf<int32_t> k_inst, k_slot, k_tick, k_r0, k_r1, k_r2, k_r3, k_act;
-    DevBuf<int64_t> k_off;
-    DevBuf<char> k_aid;
-    DevBuf<unsigned long long> k_cnt;
-    // owgs_publish_activations (owgs_publish.hip): the placed predicate, the message stage's invoker array, the output
-    // block on the device and the pinned host block it is read back into with one copy
-    DevBuf<uint8_t> p_placed, p_blk;
-    DevBuf<int32_t> p_minv;
-    void* p_pin = nullptr;
-    size_t p_pin_bytes = 0;
-    // owgs_invoke_activations (owgs_invoke.hip): the items' action handles, sequence numbers and override arrays as
-    // uploaded, the maps between an item and its rank among the admitted actions, the compaction's per-block counts
-    // (its output block and pinned block are p_blk / p_pin)
-    DevBuf<int32_t> v_act, v_map, v_rank, v_bcnt, v_ov0, v_ov1;
-    DevBuf<u64> v_seq;
-    // owgs_process_result_acks: its seven output arrays as one device block, and the pinned block they come back in
-    DevBuf<uint8_t> r_blk;
-    void* r_pin = nullptr;
-    size_t r_pin_bytes = 0;
-    // invoker health supervision (owgs_health.hip): persistent SoA by invoker id + per-batch scratch
-    DevBuf<uint8_t> h_st, he_kind, he_temp;
-    DevBuf<uint32_t> h_ring;
-    DevBuf<int64_t> h_last, h_tick, h_mem, he_t, he_mem, he_packed;
-    DevBuf<int32_t> h_tests, he_inv, he_key, he_idx0, he_idx1, he_beg, he_end, he_reg, he_pad;
-    int32_t h_cap = 0, h_size = 0;
-    // the supervision feeds (owgs_feeds.hip): the FSM kernel's summary words, the pings' receive times and parsed
-    // userMemory, and the largest batch whose feed buffers are reserved (feed_n) with its sort scratch (feed_tb)
-    DevBuf<int32_t> he_sum;
-    DevBuf<int64_t> pg_t, pg_mem;
-    int32_t feed_n = 0;
-    size_t feed_tb = 0;
-    hipEvent_t ev_engine[2] = {nullptr, nullptr};  // around the last owgs_engine_kernel launch
-    DevBuf<unsigned long long> r_bound;  // release front end scratch (owgs_launch_release_seq)
-    DevBuf<int32_t> r_idx, r_cnt, r_cval, r_cval_s, r_cbeg;
-    DevBuf<uint32_t> r_ckey, r_ckey_s;
-    DevBuf<uint8_t> r_sel, r_temp;
-    bool ev_engine_valid = false;
-    // ActivationMessage templates + serialisation scratch (owgs_msgs.hip)
-    std::vector<char> ta, tb;
-    std::vector<int64_t> ta_off{0}, tb_off{0};
-    std::string rci = "{\"asString\":\"0\"}";  // ControllerInstanceId("0"), jsonFormat1 (InstanceId.scala:40, 59)
-    bool tmpl_dirty = true;
-    DevBuf<char> m_ta, m_tb, m_rci, m_tid, m_content, m_trace, m_out;
-    DevBuf<int64_t> m_ta_off, m_tb_off, m_tid_off, m_tid_start, m_content_off, m_trace_off, m_len, m_len_sorted,
-        m_out_off;
-    DevBuf<int32_t> m_inv, m_tmpl, m_bad, m_order, m_iota, m_cnt, m_topic;
-    DevBuf<uint32_t> m_key, m_key_sorted;
-    DevBuf<ulonglong2> m_aid, m_cause;
-    DevBuf<uint8_t> m_flags, m_temp;
-    int64_t h_now = INT64_MIN;
-    // watched (invoker, fqn) pairs after a slot-state reset (owgs_watch.hip; w_cap == 0: none)
-    DevBuf<uint32_t> w_keys, w_vals;
-    DevBuf<int32_t> w_cnt, w_wkey, w_D, w_L, w_Lcnt, w_rel;
-    DevBuf<uint4> w_L2;
-    DevBuf<int64_t> w_off;
-    // owgs_replay_device_group: its batch offsets, the usable bitmap of each batch's health, and (during the call) the
-    // first activation of the group (releases of earlier ones get their records from those decisions)
-    DevBuf<int64_t> g_off;
-    // large-state engine (owgs_seq.hip): a state beyond every on-chip geometry (owgs_limits) or maxConcurrent beyond
-    // OWGS_MAX_CONC runs there -- permits in HBM, the NestedSemaphore maps in one HBM table q_map
-    bool large = false, big_conc = false;
-    DevBuf<uint4> q_map;
-    int32_t q_cap = 0;
-    DevBuf<int32_t> q_filled, q_state, q_look;
-    DevBuf<uint4> q_cur;   // walk cursors of the large-state engine, per action {generation, step, position, 0}
-    uint32_t q_gen = 1;    // the next call's first generation: cursors never outlive the call that wrote them
-    int64_t q_spec = 0, q_alone = 0;  // its decisions: kept from the group speculation / decided alone
-    int64_t q_path[OWGS_SEQ_NPATH] = {};  // ... by path (the kernel's state[16..], owgs_large_stats' [2..11])
-    int64_t q_launches = 0, q_resumes = 0;  // its launches / those that stopped for the map to grow
-    uint64_t q_cyc[4] = {0, 0, 0, 0};  // its cycles: releases, group speculation, kept decisions, decided alone
-    DevBuf<uint32_t> d_hwords;
-    const uint32_t* grp_hwords = nullptr;
-    int32_t grp_hstride = 0;
-    int64_t grp_a0 = 0;
-    DevBuf<uint8_t> w_rfl;
-    int32_t w_cap = 0, w_live = 0;
-    int32_t stats_par = 0, stats_last = 0;  // d_stats holds two counter blocks: the next launch's, the last one's
-    int32_t cw_cache = 0;  // chunk width of the current state and actions (0: recompute)
-    bool any_conc = false;  // some registered action has maxConcurrent > 1 (the engine needs its map code)
-    int32_t variant = 0;   // engine geometry: 0 wide chunks, 1 narrow (large pools, owgs_engine_narrow.hip)
-    // owgs_process_batch: pinned staging (inputs, outputs) and their device copies
-    void* h_pin = nullptr;
-    size_t h_pin_bytes = 0;
-    void* h_pout = nullptr;
-    size_t h_pout_bytes = 0;
-    DevBuf<uint8_t> d_pin, d_pout;
-    DevBuf<int32_t> f_src, f_cnt, f_tile;
-    DevBuf<uint2> f_rec;
-    // owgs_process_batch through the resident engine (owgs_resident.hip): its stream, the pinned control block and
-    // call buffers, the call counter (the doorbell), whether a launch is live, and counters for owgs_resident_stats
-    hipStream_t res_stream = nullptr;
-    hipEvent_t ev_res = nullptr;
-    int32_t* res_ctl = nullptr;
-    int32_t* res_in = nullptr;
-    char* res_out = nullptr;
-    size_t res_in_cap = 0, res_out_cap = 0;
-    int32_t res_call = 0;
-    bool res_alive = false;
-    bool res_last_served = false;  // the previous owgs_process_batch call was served by the resident engine
-    int32_t res_stage = 0;
-    int64_t res_n_calls = 0, res_n_launches = 0, res_n_bails = 0, res_n_chained = 0, res_n_life = 0;
-    int64_t res_n_watch_calls = 0;  // served calls while watched pairs existed
-    int64_t res_prof[OWGS_RES_NPROF] = {};
-    int64_t res_used_max = 0, res_tombs_max = 0;  // the primary table's fill after served calls (largest seen)
-    int64_t res_host_ns[2] = {};    // served calls: host time building the call (records, ranks), bell-to-answer wait
-    DevBuf<uint4> d_w_sidx;         // resident engine: watched pairs by fqn@version key (built at its launch)
-    DevBuf<uint2> d_w_list;
-    int32_t w_scap = 0;
-    uint64_t res_cache_epoch = 1, res_cache_seen = 0;  // res_meta / the watched-pair index are current when equal
-    DevBuf<uint2> d_res_cur;        // per action: {cursor generation, first walk step that may fit}
-    std::vector<uint2> res_meta;    // act_meta as of the live launch (every change of it stops the engine first)
-    uint32_t res_gen_seen = 0;      // the last cursor generation the engine reported
-    int64_t last_call_ns = 0;       // duration of the last publish / release / process_batch call, timed inside the library
-    DevBuf<unsigned long long> d_spec_stats;  // stream-mode replays: summed resident-engine counters (owgs_resident_stats)
-    DevBuf<uint32_t> d_claim;       // stream-mode replays: released activations (a second release is a malformed stream)
-    bool spec_last = false;         // the last replay ran in stream mode
-    DevBuf<unsigned long long> f_bound;  // per slot: what a fused call's releases can return (zero between calls)
-    DevBuf<uint32_t> s_w_keys, s_w_vals;
-    DevBuf<int32_t> s_w_wkey;
-    int32_t s_w_cap = 0, s_w_live = 0;
-    // snapshot
-    DevBuf<int32_t> s_permits;
-    DevBuf<uint32_t> s_ct_keys, s_ct_vals;
-    bool has_snap = false;
-    int32_t snap_slots = 0;
-
-    int fail(int code, const char* what, hipError_t e = hipSuccess) {
-        err = what;
-        if (e != hipSuccess) {
-            err += ": ";
-            err += hipGetErrorString(e);
-        }
-        return code;
-    }
-};
-
-#define HIPCHK(ctx, call)                                                     \
-    do {                                                                      \
-        hipError_t _e = (call);                                               \
-        if (_e != hipSuccess) return (ctx)->fail(OWGS_EDEVICE, #call, _e);    \
-    } while (0)
-
-template <class T>
-static hipError_t upload(DevBuf<T>& d, const T* h, size_t n, hipStream_t s) {
-    hipError_t e = d.reserve(n);
-    if (e != hipSuccess) return e;
-    if (n == 0) return hipSuccess;
-    return hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, s);
 }
 
 // managed = take(managed), blackbox = takeRight(blackboxes) (SCPB:522-523) -> pool words / usable bitmap, healthy
@@ -525,13 +30,13 @@ static int sync_status(owgs_ctx* c) {
 // make stream s wait for the work of the last asynchronous call when that ran on another stream (the caller may
 // free or reuse nothing of ours meanwhile: every buffer an earlier call reads belongs to the context or stays the
 // caller's until its stream reaches it, include/owgs.h)
-static int order_on(owgs_ctx* c, hipStream_t s) {
+int order_on(owgs_ctx* c, hipStream_t s) {
     if (c->tail_valid && c->tail_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_tail, 0));
     return OWGS_OK;
 }
 // the work this asynchronous call enqueued on s is the context's new tail
 static int tail_mark(owgs_ctx* c, hipStream_t s) {
-    if (!c->ev_tail) HIPCHK(c, hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming));
+    if (!c->ev_tail) HIPCHK(c, c->ev_tail.create(hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->ev_tail, s));
     c->tail_stream = s;
     c->tail_valid = true;
@@ -641,7 +146,7 @@ static hipError_t launch_engine(const owgs_ctx* c, const OwgsEngineArgs* A, hipS
     return c->variant ? owgs_launch_engine_narrow(A, s) : owgs_launch_engine(A, s);
 }
 
-static OwgsOvf ovf_args(const owgs_ctx* c) {
+OwgsOvf ovf_args(const owgs_ctx* c) {
     OwgsOvf O{};
     O.t = c->d_ovf.p;
     O.cap = c->ovf_cap;
@@ -656,7 +161,7 @@ static OwgsOvf ovf_args(const owgs_ctx* c) {
 // (an activation creates at most one (invoker, fqn) entry).  Keep it at least twice that (load <= 1/2); grow (and
 // rehash) when the bound says so -- after reading the exact entry count back once.
 // n more activations may add overflow entries: the bound grows, and so does what an outstanding count probe misses
-static void ovf_add(owgs_ctx* c, int64_t n) {
+void ovf_add(owgs_ctx* c, int64_t n) {
     c->ovf_used_ub += n;
     c->ovf_added += n;
 }
@@ -666,10 +171,10 @@ static void ovf_probes_clear(owgs_ctx* c) {
 // overflow entry-count probes: the next probe slot, or -1 while its last probe is still in flight (this launch then records none)
 static int ovf_probe_slot(owgs_ctx* c, int* k_out) {
     *k_out = -1;
-    if (!c->h_ovf_cnt) {
-        HIPCHK(c, hipHostMalloc((void**)&c->h_ovf_cnt, owgs_ctx::OVF_PROBES * sizeof(int32_t), hipHostMallocDefault));
+    if (!c->h_ovf_cnt.p) {
+        HIPCHK(c, c->h_ovf_cnt.reserve(owgs_ctx::OVF_PROBES * sizeof(int32_t), hipHostMallocDefault));
         for (int k = 0; k < owgs_ctx::OVF_PROBES; ++k)
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_ovf[k], hipEventDisableTiming));
+            HIPCHK(c, c->ev_ovf[k].create(hipEventDisableTiming));
     }
     const int k = c->ovf_probe_next;
     if (c->ovf_probe[k] && hipEventQuery(c->ev_ovf[k]) != hipSuccess) return OWGS_OK;  // (still in flight: skip)
@@ -707,7 +212,7 @@ static int ovf_probe_refresh(owgs_ctx* c, bool wait_older) {
             (best < 0 || c->ovf_probe_added[k] > c->ovf_probe_added[best]))
             best = k;
     if (best < 0) return OWGS_OK;
-    c->ovf_used_ub = std::min(c->ovf_used_ub, (int64_t)c->h_ovf_cnt[best] + (c->ovf_added - c->ovf_probe_added[best]));
+    c->ovf_used_ub = std::min(c->ovf_used_ub, (int64_t)c->h_ovf_cnt.p[best] + (c->ovf_added - c->ovf_probe_added[best]));
     for (int k = 0; k < owgs_ctx::OVF_PROBES; ++k)  // this probe and older ones are consumed
         if (c->ovf_probe[k] && c->ovf_probe_added[k] <= c->ovf_probe_added[best]) c->ovf_probe[k] = false;
     return OWGS_OK;
@@ -722,7 +227,7 @@ static int64_t ovf_need(int64_t used, int64_t n_new) {
     return cap;
 }
 
-static int ensure_ovf(owgs_ctx* c, int64_t n_new, hipStream_t s) {
+int ensure_ovf(owgs_ctx* c, int64_t n_new, hipStream_t s) {
     auto need = [&](int64_t used) { return ovf_need(used, n_new); };
     if (c->ovf_cap >= need(c->ovf_used_ub)) return OWGS_OK;
     {  // a count that arrived meanwhile, else one of an older launch (the GPU keeps the later ones)
@@ -758,9 +263,7 @@ static int ensure_ovf(owgs_ctx* c, int64_t n_new, hipStream_t s) {
         HIPCHK(c, owgs_launch_ovf_rehash(c->d_ovf.p, c->ovf_cap, &O, c->d_err.p, s));
     }
     HIPCHK(c, hipStreamSynchronize(s));
-    c->d_ovf.release();
-    c->d_ovf = nt;
-    nt.p = nullptr;
+    c->d_ovf = std::move(nt);
     c->ovf_cap = (int32_t)cap;
     return OWGS_OK;
 }
@@ -780,7 +283,7 @@ static int reset_ctab(owgs_ctx* c) {
 }
 
 // ---------------------------------------------------------------------------------------------- watched pairs
-static OwgsWatch watch_args(const owgs_ctx* c) {
+OwgsWatch watch_args(const owgs_ctx* c) {
     OwgsWatch w{};
     if (c->w_cap > 0) {
         w.keys = c->w_keys.p;
@@ -802,7 +305,7 @@ static void w_drop(owgs_ctx* c) {
 }
 
 // after a call that may have taken pairs out of W (a release that threw NoSuchElement): its live count
-static int w_refresh(owgs_ctx* c, hipStream_t s) {
+int w_refresh(owgs_ctx* c, hipStream_t s) {
     if (c->w_cap <= 0) return OWGS_OK;
     int32_t live = 0;
     HIPCHK(c, hipMemcpyAsync(&live, c->w_cnt.p, sizeof(live), hipMemcpyDeviceToHost, s));
@@ -850,22 +353,16 @@ static int w_rebuild(owgs_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(s));
     w_drop(c);
     if (live > 0) {
-        c->w_keys = nk;
-        c->w_vals = nv;
-        c->w_wkey = nw;
-        nk.p = nv.p = nullptr;
-        nw.p = nullptr;
+        c->w_keys = std::move(nk);
+        c->w_vals = std::move(nv);
+        c->w_wkey = std::move(nw);
         c->w_cap = (int32_t)cap;
         c->w_live = live;
-    } else {
-        nk.release();
-        nv.release();
-        nw.release();
     }
     return OWGS_OK;
 }
 
-static void base_args(owgs_ctx* c, OwgsEngineArgs& A) {
+void base_args(owgs_ctx* c, OwgsEngineArgs& A) {
     memset(&A, 0, sizeof(A));
     A.permits = c->d_permits.p;
     A.n_slots = c->n_slots;
@@ -930,8 +427,8 @@ static int32_t chunk_width(owgs_ctx* c) {
 }
 
 // chunk records of n_act activations (act != null: registered actions; else explicit per-activation walks)
-static int run_prepass(owgs_ctx* c, OwgsEngineArgs& A, int32_t n_batches, const int64_t* acq_off, const int32_t* act,
-                       int64_t n_act, hipStream_t s) {
+int run_prepass(owgs_ctx* c, OwgsEngineArgs& A, int32_t n_batches, const int64_t* acq_off, const int32_t* act,
+                int64_t n_act, hipStream_t s) {
     HIPCHK(c, c->d_rec.reserve((size_t)std::max<int64_t>(n_act, 1)));
     HIPCHK(c, c->d_cstart.reserve((size_t)n_batches + 1));
     int rv = lds_check(c);  // the engine geometry decides the chunk width and the record layout
@@ -968,7 +465,7 @@ static int run_prepass(owgs_ctx* c, OwgsEngineArgs& A, int32_t n_batches, const 
     return OWGS_OK;
 }
 
-static int run_engine(owgs_ctx* c, OwgsEngineArgs& A, hipStream_t s, bool launch = true) {
+int run_engine(owgs_ctx* c, OwgsEngineArgs& A, hipStream_t s, bool launch) {
     int rc = lds_check(c);
     if (rc) return rc;
     // the map's overflow exists only for concurrent actions: a context without any never allocates it
@@ -997,8 +494,8 @@ static int run_engine(owgs_ctx* c, OwgsEngineArgs& A, hipStream_t s, bool launch
     c->stats_last = c->stats_par;
     c->stats_par ^= 1;
     if (!c->ev_engine[0]) {
-        HIPCHK(c, hipEventCreate(&c->ev_engine[0]));
-        HIPCHK(c, hipEventCreate(&c->ev_engine[1]));
+        HIPCHK(c, c->ev_engine[0].create());
+        HIPCHK(c, c->ev_engine[1].create());
     }
     // the engine specialisation: the map code when any registered action is concurrent (its entries, releases and
     // overflow can only come from such actions), the general pool / sequence code when the call needs it
@@ -1012,7 +509,7 @@ static int run_engine(owgs_ctx* c, OwgsEngineArgs& A, hipStream_t s, bool launch
     if (c->ovf_cap > 0) {
         const int rc = ovf_probe_slot(c, &probe);
         if (rc) return rc;
-        if (probe >= 0) A.ovf_host = &c->h_ovf_cnt[probe];
+        if (probe >= 0) A.ovf_host = &c->h_ovf_cnt.p[probe];
     }
     HIPCHK(c, hipEventRecord(c->ev_engine[0], s));  // brackets exactly the engine launch (owgs_engine_ms)
     HIPCHK(c, launch_engine(c, &A, s));
@@ -1036,8 +533,8 @@ static int run_engine(owgs_ctx* c, OwgsEngineArgs& A, hipStream_t s, bool launch
 
 // after a publish run in watch mode: Z of the watched pairs its decisions tried and failed (owgs_watch.hip).  d_act =
 // the run's action handles (device), or null for explicit walks (d_xmeta / d_xslot of owgs_schedule_walks)
-static int w_update(owgs_ctx* c, int32_t n, const int32_t* d_act, const int32_t* d_out, const uint8_t* d_fl,
-                    hipStream_t s) {
+int w_update(owgs_ctx* c, int32_t n, const int32_t* d_act, const int32_t* d_out, const uint8_t* d_fl,
+             hipStream_t s) {
     if (c->w_cap <= 0 || n <= 0) return OWGS_OK;
     const size_t na = std::max<size_t>(c->a_mem.size(), 1);
     const size_t had = c->w_D.n;
@@ -1073,7 +570,7 @@ static int w_update(owgs_ctx* c, int32_t n, const int32_t* d_act, const int32_t*
     return OWGS_OK;
 }
 
-static int check_err_word(owgs_ctx* c) {
+int check_err_word(owgs_ctx* c) {
     int32_t e = 0;
     HIPCHK(c, hipMemcpy(&e, c->d_err.p, sizeof(int32_t), hipMemcpyDeviceToHost));
     if (e) {
@@ -1092,7 +589,7 @@ static int check_err_word(owgs_ctx* c) {
     return OWGS_OK;
 }
 
-static bool registered(const owgs_ctx* c, int32_t n, const int32_t* action) {
+bool registered(const owgs_ctx* c, int32_t n, const int32_t* action) {
     const int32_t na = (int32_t)c->a_mem.size();
     for (int32_t i = 0; i < n; ++i)
         if (action[i] < 0 || action[i] >= na || !c->a_live[action[i]]) return false;
@@ -1146,10 +643,10 @@ static int reclaim_slots(owgs_ctx* c) {
 // writes the state back to HBM and exits) -- OWGS_ENTER below; the next eligible call launches it again.
 // after the engine's stream has drained: count an exit the lifetime bound caused (diagnostics)
 static void res_reap(owgs_ctx* c) {
-    if (__atomic_load_n(&c->res_ctl[OWGS_RES_STATE], __ATOMIC_ACQUIRE) == 2 &&
-        __atomic_load_n(&c->res_ctl[OWGS_RES_WHY], __ATOMIC_ACQUIRE) == 2)
+    if (__atomic_load_n(&c->res_ctl.p[OWGS_RES_STATE], __ATOMIC_ACQUIRE) == 2 &&
+        __atomic_load_n(&c->res_ctl.p[OWGS_RES_WHY], __ATOMIC_ACQUIRE) == 2)
         ++c->res_n_life;
-    c->res_ctl[OWGS_RES_STATE] = 0;
+    c->res_ctl.p[OWGS_RES_STATE] = 0;
 }
 // the exited engine wrote its primary table back, possibly compacted by its cleanup between calls: the chunked engine's
 // rebuild mark (d_clast) describes the table before that and would delay the next rebuild.  (The engine's stream has
@@ -1159,22 +656,15 @@ static int res_clear_mark(owgs_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->res_stream));
     return OWGS_OK;
 }
-static int res_quiesce(owgs_ctx* c) {
+int res_quiesce(owgs_ctx* c) {
     if (!c->res_alive) return OWGS_OK;
-    __atomic_store_n(&c->res_ctl[OWGS_RES_BELL], -1, __ATOMIC_RELEASE);
+    __atomic_store_n(&c->res_ctl.p[OWGS_RES_BELL], -1, __ATOMIC_RELEASE);
     c->res_alive = false;
     HIPCHK(c, hipStreamSynchronize(c->res_stream));
     res_reap(c);
     if (c->w_cap > 0 && c->w_live <= 0) w_drop(c);  // the engine's calls took the last pairs out of W
     return res_clear_mark(c);
 }
-
-#define OWGS_ENTER(c)                             \
-    do {                                          \
-        (void)hipSetDevice((c)->cfg.device);      \
-        const int q_ = res_quiesce(c);            \
-        if (q_) return q_;                        \
-    } while (0)
 
 static size_t res_stage_bytes(const owgs_ctx* c) {
     const size_t img = owgs_resident_image_bytes(c->n_slots, c->n_ids);
@@ -1280,11 +770,11 @@ static int res_w_index(owgs_ctx* c) {
 }
 
 static int res_launch(owgs_ctx* c) {
-    if (!c->res_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->res_stream, hipStreamNonBlocking));
-    if (!c->ev_res) HIPCHK(c, hipEventCreateWithFlags(&c->ev_res, hipEventDisableTiming));
-    if (!c->res_ctl) {
-        HIPCHK(c, hipHostMalloc((void**)&c->res_ctl, OWGS_RES_CTL_WORDS * sizeof(int32_t), hipHostMallocCoherent));
-        memset(c->res_ctl, 0, OWGS_RES_CTL_WORDS * sizeof(int32_t));
+    if (!c->res_stream) HIPCHK(c, c->res_stream.create(hipStreamNonBlocking));
+    if (!c->ev_res) HIPCHK(c, c->ev_res.create(hipEventDisableTiming));
+    if (!c->res_ctl.p) {
+        HIPCHK(c, c->res_ctl.reserve(OWGS_RES_CTL_WORDS * sizeof(int32_t), hipHostMallocCoherent));
+        memset(c->res_ctl.p, 0, OWGS_RES_CTL_WORDS * sizeof(int32_t));
     }
     if (c->any_conc) {  // the map's overflow, sized for this call (before the engine holds the table)
         const int rc = ensure_ovf(c, env_opts().res_max, c->stream);
@@ -1346,9 +836,9 @@ static int res_launch(owgs_ctx* c) {
     a.n_actions = (int32_t)c->a_mem.size();
     a.rng_seed = c->cfg.rng_seed;
     a.err = c->d_err.p;
-    a.ctl = c->res_ctl;
-    a.in = c->res_in;
-    a.out = c->res_out;
+    a.ctl = c->res_ctl.p;
+    a.in = c->res_in.p;
+    a.out = c->res_out.p;
     a.stage_bytes = (int32_t)res_stage_bytes(c);
     a.last_call = c->res_call;
     a.cur = c->d_res_cur.p;  // (dropping them measured slower: drains inside a batch's publishes keep the generation)
@@ -1364,11 +854,11 @@ static int res_launch(owgs_ctx* c) {
     a.w_sidx = c->d_w_sidx.p;
     a.w_scap = c->w_scap;
     a.w_list = c->d_w_list.p;
-    if (c->w_cap > 0) c->res_ctl[OWGS_RES_WLIVE] = c->w_live;
-    volatile int32_t* ctl = c->res_ctl;
+    if (c->w_cap > 0) c->res_ctl.p[OWGS_RES_WLIVE] = c->w_live;
+    volatile int32_t* ctl = c->res_ctl.p;
     ctl[OWGS_RES_STATE] = 0;
     ctl[OWGS_RES_DONE] = c->res_call;
-    __atomic_store_n(&c->res_ctl[OWGS_RES_BELL], c->res_call, __ATOMIC_RELEASE);
+    __atomic_store_n(&c->res_ctl.p[OWGS_RES_BELL], c->res_call, __ATOMIC_RELEASE);
     const size_t lds = owgs_resident_image_bytes(c->n_slots, c->n_ids) + (size_t)a.stage_bytes;
     HIPCHK(c, owgs_launch_resident(&a, lds, c->res_stream));
     c->res_alive = true;
@@ -1393,25 +883,13 @@ static int res_process(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, cons
     const size_t b_seq = b_pub + al(4 * (size_t)NR);
     const size_t in_bytes = al(b_seq + (seq ? 8 * (size_t)NP : 0));
     const size_t o_fl = 4 * (size_t)NP, o_rfl = o_fl + NP, out_bytes = al(o_rfl + NR) + 16;
-    if (std::max<size_t>(in_bytes, 4096) > c->res_in_cap || out_bytes > c->res_out_cap) {  // (the engine holds the
+    if (std::max<size_t>(in_bytes, 4096) > c->res_in.bytes || out_bytes > c->res_out.bytes) {  // (the engine holds the
         const int q = res_quiesce(c);                                                        // buffers' addresses)
         if (q) return q;
-        if (std::max<size_t>(in_bytes, 4096) > c->res_in_cap) {
-            if (c->res_in) (void)hipHostFree(c->res_in);
-            c->res_in = nullptr;
-            c->res_in_cap = 0;
-            const size_t cap = std::max<size_t>(2 * in_bytes, 64 * 1024);
-            HIPCHK(c, hipHostMalloc((void**)&c->res_in, cap, hipHostMallocCoherent));
-            c->res_in_cap = cap;
-        }
-        if (out_bytes > c->res_out_cap) {
-            if (c->res_out) (void)hipHostFree(c->res_out);
-            c->res_out = nullptr;
-            c->res_out_cap = 0;
-            const size_t cap = std::max<size_t>(2 * out_bytes, 32 * 1024);
-            HIPCHK(c, hipHostMalloc((void**)&c->res_out, cap, hipHostMallocCoherent));
-            c->res_out_cap = cap;
-        }
+        if (std::max<size_t>(in_bytes, 4096) > c->res_in.bytes)
+            HIPCHK(c, c->res_in.reserve(std::max<size_t>(2 * in_bytes, 64 * 1024), hipHostMallocCoherent));
+        if (out_bytes > c->res_out.bytes)
+            HIPCHK(c, c->res_out.reserve(std::max<size_t>(2 * out_bytes, 32 * 1024), hipHostMallocCoherent));
     }
     // the doorbell and the cursor generation stay below their limits: an engine near either is stopped (it writes
     // the state back) and the relaunch below starts both over
@@ -1424,7 +902,7 @@ static int res_process(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, cons
         const int rc = res_launch(c);
         if (rc) return rc;
     }
-    char* B = (char*)c->res_in;
+    char* B = (char*)c->res_in.p;
     memcpy(B, rel_off, 4 * ((size_t)n_runs + 1));
     memcpy(B + b_poff, pub_off, 4 * ((size_t)n_runs + 1));
     if (NR) {
@@ -1486,7 +964,7 @@ static int res_process(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, cons
             }
     }
     if (seq && NP) memcpy(B + b_seq, seq, 8 * (size_t)NP);
-    volatile int32_t* H = c->res_ctl + OWGS_RES_HDR;
+    volatile int32_t* H = c->res_ctl.p + OWGS_RES_HDR;
     const int32_t hdr[14] = {n_runs, NR, NP, seq ? 1 : 0, (int32_t)(uint32_t)seq_base, (int32_t)(uint32_t)(seq_base >> 32),
                              (int32_t)b_poff, (int32_t)b_rel, (int32_t)b_pub, (int32_t)b_seq, (int32_t)in_bytes,
                              (int32_t)(uint32_t)rsum, (int32_t)(uint32_t)(rsum >> 32), (int32_t)b_aid};
@@ -1494,13 +972,13 @@ static int res_process(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, cons
     const auto th1 = std::chrono::steady_clock::now();
     for (int attempt = 0;; ++attempt) {
         const int32_t k = ++c->res_call;
-        __atomic_store_n(&c->res_ctl[OWGS_RES_BELL], k, __ATOMIC_RELEASE);
+        __atomic_store_n(&c->res_ctl.p[OWGS_RES_BELL], k, __ATOMIC_RELEASE);
         const auto t0 = std::chrono::steady_clock::now();
         bool exited = false;
         for (long spin = 0;; ++spin) {
-            if (__atomic_load_n(&c->res_ctl[OWGS_RES_DONE], __ATOMIC_ACQUIRE) == k) break;
-            if (__atomic_load_n(&c->res_ctl[OWGS_RES_STATE], __ATOMIC_ACQUIRE) == 2 &&
-                __atomic_load_n(&c->res_ctl[OWGS_RES_DONE], __ATOMIC_ACQUIRE) != k) {
+            if (__atomic_load_n(&c->res_ctl.p[OWGS_RES_DONE], __ATOMIC_ACQUIRE) == k) break;
+            if (__atomic_load_n(&c->res_ctl.p[OWGS_RES_STATE], __ATOMIC_ACQUIRE) == 2 &&
+                __atomic_load_n(&c->res_ctl.p[OWGS_RES_DONE], __ATOMIC_ACQUIRE) != k) {
                 exited = true;  // it went idle and wrote the state back before it saw this call
                 break;
             }
@@ -1520,7 +998,7 @@ static int res_process(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, cons
         const int rc = res_launch(c);
         if (rc) return rc;
     }
-    const int32_t res = __atomic_load_n(&c->res_ctl[OWGS_RES_RESULT], __ATOMIC_ACQUIRE);
+    const int32_t res = __atomic_load_n(&c->res_ctl.p[OWGS_RES_RESULT], __ATOMIC_ACQUIRE);
     const int bail = res & 0xFF, e = res >> 8;
     {
         const auto th2 = std::chrono::steady_clock::now();
@@ -1533,19 +1011,19 @@ static int res_process(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, cons
     }
     ++c->res_n_calls;
     if (c->w_cap > 0) {  // watched pairs left (W itself is dropped once the engine has stopped: res_quiesce)
-        c->w_live = __atomic_load_n(&c->res_ctl[OWGS_RES_WLIVE], __ATOMIC_ACQUIRE);
+        c->w_live = __atomic_load_n(&c->res_ctl.p[OWGS_RES_WLIVE], __ATOMIC_ACQUIRE);
         ++c->res_n_watch_calls;
     }
-    c->res_gen_seen = (uint32_t)__atomic_load_n(&c->res_ctl[OWGS_RES_GEN], __ATOMIC_ACQUIRE);
-    for (int k = 0; k < OWGS_RES_NPROF; ++k) c->res_prof[k] += (uint32_t)c->res_ctl[OWGS_RES_PROF + k];
-    c->res_used_max = std::max<int64_t>(c->res_used_max, c->res_ctl[OWGS_RES_USED]);
-    c->res_tombs_max = std::max<int64_t>(c->res_tombs_max, c->res_ctl[OWGS_RES_TOMBS]);
+    c->res_gen_seen = (uint32_t)__atomic_load_n(&c->res_ctl.p[OWGS_RES_GEN], __ATOMIC_ACQUIRE);
+    for (int k = 0; k < OWGS_RES_NPROF; ++k) c->res_prof[k] += (uint32_t)c->res_ctl.p[OWGS_RES_PROF + k];
+    c->res_used_max = std::max<int64_t>(c->res_used_max, c->res_ctl.p[OWGS_RES_USED]);
+    c->res_tombs_max = std::max<int64_t>(c->res_tombs_max, c->res_ctl.p[OWGS_RES_TOMBS]);
     if (c->any_conc) ovf_add(c, NP);
     if (NP) {
-        memcpy(out_invoker, c->res_out, 4 * (size_t)NP);
-        memcpy(out_flags, c->res_out + o_fl, (size_t)NP);
+        memcpy(out_invoker, c->res_out.p, 4 * (size_t)NP);
+        memcpy(out_flags, c->res_out.p + o_fl, (size_t)NP);
     }
-    if (NR && rel_flags) memcpy(rel_flags, c->res_out + o_rfl, (size_t)NR);
+    if (NR && rel_flags) memcpy(rel_flags, c->res_out.p + o_rfl, (size_t)NR);
     *served = 1;
     if (e) {
         if (e & OWGS_ERR_CTAB_FULL) return c->fail(OWGS_ENOMEM, "concurrency table full");
@@ -1560,17 +1038,11 @@ static int res_process(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, cons
 // ---------------------------------------------------------------------------------------------- large-state engine
 // owgs_seq.hip: contexts whose state no on-chip geometry holds (owgs_limits), or with maxConcurrent > OWGS_MAX_CONC.
 // Identity pools; every call through it is synchronous (the host reads where the kernel stopped to grow the map).
-#define OWGS_NOT_LARGE(c)                                                                                   \
-    do {                                                                                                  \
-        if ((c)->large)                                                                                   \
-            return (c)->fail(OWGS_ERANGE, "not available for a state beyond owgs_limits (large-state engine)"); \
-    } while (0)
-
 static bool large_fits(int32_t n_ids, int32_t nm, int32_t nb) {
     return n_ids <= OWGS_SEQ_MAX_WORDS * 32 && nm <= owgs_coprime_max() && nb <= owgs_coprime_max();
 }
 
-static OwgsSeqArgs seq_args(owgs_ctx* c) {
+OwgsSeqArgs seq_args(owgs_ctx* c) {
     OwgsSeqArgs S{};
     S.permits = c->d_permits.p;
     S.n_slots = c->n_slots;
@@ -1626,9 +1098,7 @@ static int seq_reserve(owgs_ctx* c, int64_t room, hipStream_t s) {
         HIPCHK(c, owgs_launch_seq_rehash(c->q_map.p, c->q_cap, &S, s));
         HIPCHK(c, hipStreamSynchronize(s));
     }
-    c->q_map.release();
-    c->q_map = nt;
-    nt.p = nullptr;
+    c->q_map = std::move(nt);
     c->q_cap = (int32_t)cap;
     return OWGS_OK;
 }
@@ -1657,7 +1127,7 @@ static int seq_migrate(owgs_ctx* c) {
 }
 
 // runs through the large-state engine (S: its runs, releases, publishes, outputs); resumes after map growth
-static int seq_run(owgs_ctx* c, const OwgsSeqArgs& S0, hipStream_t s) {
+int seq_run(owgs_ctx* c, const OwgsSeqArgs& S0, hipStream_t s) {
     const int64_t room = 2 * ((int64_t)std::max(c->nm, c->nb) + 2) + 4096;
     // walk cursors: one per action, tagged with a generation that no earlier call used (state changes between calls
     // -- health, cluster size, restores -- need no invalidation); all zero again before the counter could wrap
@@ -1667,10 +1137,7 @@ static int seq_run(owgs_ctx* c, const OwgsSeqArgs& S0, hipStream_t s) {
         HIPCHK(c, nc.reserve(na + na / 2 + 64));
         HIPCHK(c, hipMemsetAsync(nc.p, 0, nc.n * sizeof(uint4), s));
         HIPCHK(c, hipStreamSynchronize(s));
-        c->q_cur.release();
-        c->q_cur = nc;
-        nc.p = nullptr;
-        nc.n = 0;
+        c->q_cur = std::move(nc);
     }
     if (c->q_gen > 0xF0000000u) {
         if (c->q_cur.p) HIPCHK(c, hipMemsetAsync(c->q_cur.p, 0, c->q_cur.n * sizeof(uint4), s));
@@ -1770,19 +1237,6 @@ static int seq_device_runs(owgs_ctx* c, int32_t n_runs, const int64_t* d_rel_off
     return seq_run(c, S, s);
 }
 
-// times one ABI call, entry to return, into c->last_call_ns (the latency the JNI shim sees, without the host
-// language's call overhead)
-struct CallTimer {
-    owgs_ctx* c;
-    std::chrono::steady_clock::time_point t0;
-    explicit CallTimer(owgs_ctx* c_) : c(c_), t0(std::chrono::steady_clock::now()) {}
-    ~CallTimer() {
-        if (c) c->last_call_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-    }
-};
-
-extern "C" {
-
 int owgs_abi_version(void) { return OWGS_ABI_VERSION; }
 
 // Diagnostics: both engine objects refuse a launch prepared for the other geometry before anything runs (the launch
@@ -1834,7 +1288,7 @@ int owgs_create(const owgs_config* cfg, owgs_ctx** out) {
         delete c;
         return OWGS_EDEVICE;
     }
-    if (hipSetDevice(cfg->device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (hipSetDevice(cfg->device) != hipSuccess || c->stream.create(hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return OWGS_EDEVICE;
     }
@@ -1865,163 +1319,8 @@ void owgs_destroy(owgs_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     (void)res_quiesce(c);
-    if (c->res_stream) (void)hipStreamDestroy(c->res_stream);
-    c->res_stream = nullptr;
-    if (c->ev_res) (void)hipEventDestroy(c->ev_res);
-    c->ev_res = nullptr;
-    if (c->res_ctl) (void)hipHostFree(c->res_ctl);
-    if (c->res_in) (void)hipHostFree(c->res_in);
-    if (c->res_out) (void)hipHostFree(c->res_out);
-    c->res_ctl = c->res_in = nullptr;
-    c->res_out = nullptr;
-    c->d_res_cur.release();
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    DevBuf<int32_t>* i32s[] = {&c->d_permits, &c->d_pool_words, &c->d_hlist, &c->d_act_slot, &c->d_act_hash,
-                               &c->d_act_mem,  &c->d_act_maxc,   &c->d_steps,  &c->d_cpx,     &c->d_err,
-                               &c->d_a,        &c->d_b,          &c->d_c,      &c->d_d,        &c->d_out,
-                               &c->d_cstart,   &c->d_relx,       &c->d_relcnt, &c->d_xslot,  &c->s_permits};
-    for (auto* b : i32s) b->release();
-    DevBuf<uint32_t>* u32s[] = {&c->d_usable, &c->d_ct_keys, &c->d_ct_vals, &c->d_ct_tmp, &c->s_ct_keys, &c->s_ct_vals};
-    for (auto* b : u32s) b->release();
-    c->d_act_bb.release();
-    c->q_map.release();
-    c->q_filled.release();
-    c->q_state.release();
-    c->q_cur.release();
-    c->q_look.release();
-    c->d_act_cok.release();
-    c->d_act_meta.release();
-    c->d_stats.release();
-    c->d_margs.release();
-    c->d_ovf.release();
-    c->s_ovf.release();
-    c->d_ovf_rc.release();
-    c->d_ovf_touched.release();
-    c->d_ovf_cnt.release();
-    if (c->h_margs) (void)hipHostFree(c->h_margs);
-    c->h_margs = nullptr;
-    if (c->h_ovf_cnt) (void)hipHostFree(c->h_ovf_cnt);
-    c->h_ovf_cnt = nullptr;
-    for (int k = 0; k < owgs_ctx::OVF_PROBES; ++k) {
-        if (c->ev_ovf[k]) (void)hipEventDestroy(c->ev_ovf[k]);
-        c->ev_ovf[k] = nullptr;
-    }
-    if (c->ev_status) (void)hipEventDestroy(c->ev_status);
-    c->ev_status = nullptr;
-    if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
-    c->ev_tail = nullptr;
-    if (c->ev_margs) (void)hipEventDestroy(c->ev_margs);
-    c->ev_margs = nullptr;
-    c->d_off.release();
-    c->d_flags.release();
-    c->d_rflags.release();
-    c->d_seq.release();
-    c->d_rel.release();
-    c->d_rec.release();
-    c->d_lix.release();
-    c->d_gcur.release();
-    c->d_trace.release();
-    c->d_rel_rec.release();
-    c->d_xmeta.release();
-    c->t_tw.release();
-    c->t_tk.release();
-    c->t_tv.release();
-    c->t_tn.release();
-    c->t_owner.release();
-    DevBuf<long long>* x64[] = {&c->t_td, &c->t_tmin, &c->x_d, &c->x_tl, &c->x_outd};
-    for (auto* b : x64) b->release();
-    DevBuf<int32_t>* x32[] = {&c->t_ti, &c->x_slot, &c->x_idx0, &c->x_idx1, &c->x_cnt, &c->x_inv};
-    for (auto* b : x32) b->release();
-    DevBuf<unsigned long long>* xu[] = {&c->t_tq, &c->x_q, &c->x_key, &c->x_key_s};
-    for (auto* b : xu) b->release();
-    c->x_temp.release();
-    c->d_ns_active.release();
-    c->d_rate_min.release();
-    c->d_rate_cnt.release();
-    c->g_min.release();
-    c->g_out.release();
-    if (c->g_pin) (void)hipHostFree(c->g_pin);
-    c->g_pin = nullptr;
-    c->q_key.release();
-    c->q_idx0.release();
-    c->q_idx1.release();
-    c->q_temp.release();
-    c->k_key.release();
-    c->k_info.release();
-    c->k_state.release();
-    c->k_kind.release();
-    c->k_oflags.release();
-    c->k_bytes.release();
-    c->k_cfl.release();
-    DevBuf<int32_t>* ks[] = {&c->k_inst, &c->k_slot, &c->k_tick, &c->k_r0, &c->k_r1, &c->k_r2, &c->k_r3, &c->k_act};
-    for (auto* b : ks) b->release();
-    c->k_off.release();
-    c->k_aid.release();
-    c->k_cnt.release();
-    c->p_placed.release();
-    c->p_blk.release();
-    c->p_minv.release();
-    DevBuf<int32_t>* vs[] = {&c->v_act, &c->v_map, &c->v_rank, &c->v_bcnt, &c->v_ov0, &c->v_ov1};
-    for (auto* b : vs) b->release();
-    c->v_seq.release();
-    if (c->p_pin) (void)hipHostFree(c->p_pin);
-    c->p_pin = nullptr;
-    c->r_blk.release();
-    if (c->r_pin) (void)hipHostFree(c->r_pin);
-    c->r_pin = nullptr;
-    DevBuf<char>* mc[] = {&c->m_ta, &c->m_tb, &c->m_rci, &c->m_tid, &c->m_content, &c->m_trace, &c->m_out};
-    for (auto* b : mc) b->release();
-    DevBuf<int64_t>* m64[] = {&c->m_ta_off, &c->m_tb_off, &c->m_tid_off, &c->m_tid_start, &c->m_content_off,
-                              &c->m_trace_off, &c->m_len, &c->m_len_sorted, &c->m_out_off};
-    for (auto* b : m64) b->release();
-    DevBuf<int32_t>* m32[] = {&c->m_inv, &c->m_tmpl, &c->m_bad, &c->m_order, &c->m_iota, &c->m_cnt, &c->m_topic};
-    for (auto* b : m32) b->release();
-    c->m_key.release();
-    c->m_key_sorted.release();
-    c->m_aid.release();
-    c->m_cause.release();
-    c->m_flags.release();
-    c->m_temp.release();
-    DevBuf<uint32_t>* wu[] = {&c->w_keys, &c->w_vals, &c->s_w_keys, &c->s_w_vals};
-    for (auto* b : wu) b->release();
-    DevBuf<int32_t>* wi[] = {&c->w_cnt, &c->w_wkey, &c->w_D, &c->w_L, &c->w_Lcnt, &c->w_rel, &c->s_w_wkey};
-    for (auto* b : wi) b->release();
-    c->w_L2.release();
-    c->w_off.release();
-    c->w_rfl.release();
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
-    if (c->h_pout) (void)hipHostFree(c->h_pout);
-    c->h_pin = c->h_pout = nullptr;
-    c->d_pin.release();
-    c->d_pout.release();
-    c->f_src.release();
-    c->f_cnt.release();
-    c->f_tile.release();
-    c->f_rec.release();
-    c->f_bound.release();
-    c->r_bound.release();
-    c->r_idx.release();
-    c->r_cnt.release();
-    c->r_sel.release();
-    c->r_temp.release();
-    c->r_cval.release();
-    c->r_cval_s.release();
-    c->r_cbeg.release();
-    c->r_ckey.release();
-    c->r_ckey_s.release();
-    c->h_st.release();
-    c->he_kind.release();
-    c->he_temp.release();
-    c->h_ring.release();
-    DevBuf<int64_t>* h64[] = {&c->h_last, &c->h_tick, &c->h_mem,  &c->he_t,
-                              &c->he_mem, &c->he_packed, &c->pg_t, &c->pg_mem};
-    for (auto* b : h64) b->release();
-    DevBuf<int32_t>* h32[] = {&c->h_tests, &c->he_inv, &c->he_key, &c->he_idx0, &c->he_idx1,
-                              &c->he_beg,  &c->he_end, &c->he_reg, &c->he_pad,  &c->he_sum};
-    for (auto* b : h32) b->release();
-    if (c->ev_engine[0]) (void)hipEventDestroy(c->ev_engine[0]);
-    if (c->ev_engine[1]) (void)hipEventDestroy(c->ev_engine[1]);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    // buffers and pinned blocks, then events, then the streams: the context's member order (struct owgs_ctx)
     delete c;
 }
 
@@ -2097,9 +1396,7 @@ int owgs_update_invokers(owgs_ctx* c, int32_t n, const int32_t* ids, const int64
             HIPCHK(c, owgs_launch_slots(c->d_mem_bytes.p, c->n_slots, n, c->cluster, c->cfg.min_memory_bytes, nb.p,
                                         c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            c->d_permits.release();
-            c->d_permits = nb;
-            nb.p = nullptr;
+            c->d_permits = std::move(nb);
             c->n_slots = n;
         }
     }
@@ -2269,11 +1566,6 @@ int owgs_register_actions(owgs_ctx* c, int32_t n, const char* ns_bytes, const in
     std::vector<int32_t> h(n);
     HIPCHK(c, hipMemcpyAsync(h.data(), dh.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    dns.release();
-    dpath.release();
-    dnso.release();
-    dpo.release();
-    dh.release();
     for (int32_t i = 0; i < n; ++i) {
         c->a_hash[hid[i]] = h[i];
         if (out_hash) out_hash[i] = h[i];
@@ -2318,15 +1610,13 @@ int owgs_release_actions(owgs_ctx* c, int32_t n, const int32_t* actions) {
     return OWGS_OK;
 }
 
-}  // extern "C"
-
 // The device half of the scheduling step (SCPB:257-290) for n activations, shared by owgs_publish_batch and
 // owgs_publish_activations: the launch chain of an on-chip context (with the watched pairs' update), or the
 // large-state engine.  The decisions stay in c->d_out / c->d_flags and the action handles in c->d_a, queued on the
 // context's stream.  On a large-state context the engine's run synchronises and reports its own errors; h_out /
 // h_flags (nullable) then also receive the decisions as seq_host_runs copies them.
-static int publish_device(owgs_ctx* c, int32_t n, const int32_t* action, const uint64_t* seq, uint64_t seq_base,
-                          int32_t* h_out, uint8_t* h_flags) {
+int publish_device(owgs_ctx* c, int32_t n, const int32_t* action, const uint64_t* seq, uint64_t seq_base,
+                   int32_t* h_out, uint8_t* h_flags) {
     if (c->large) {
         const int32_t ro[2] = {0, 0}, po[2] = {0, n};
         return seq_host_runs(c, 1, ro, nullptr, nullptr, nullptr, po, action, seq, seq_base, h_out, h_flags);
@@ -2349,8 +1639,6 @@ static int publish_device(owgs_ctx* c, int32_t n, const int32_t* action, const u
     return rc;
 }
 
-extern "C" {
-
 int owgs_publish_batch(owgs_ctx* c, int32_t n, const int32_t* action, const uint64_t* seq, uint64_t seq_base,
                        int32_t* out_invoker, uint8_t* out_flags) {
     if (!c || n < 0 || (n > 0 && (!action || !out_invoker || !out_flags))) return OWGS_EINVAL;
@@ -2371,7 +1659,7 @@ int owgs_publish_batch(owgs_ctx* c, int32_t n, const int32_t* action, const uint
 }
 
 // scratch of the release front end for n releases
-static int release_scratch(owgs_ctx* c, OwgsReleaseArgs& R, int32_t n) {
+int release_scratch(owgs_ctx* c, OwgsReleaseArgs& R, int32_t n) {
     HIPCHK(c, c->r_bound.reserve((size_t)std::max(c->n_slots, 1)));
     HIPCHK(c, c->r_idx.reserve((size_t)std::max(n, 1)));
     HIPCHK(c, c->r_sel.reserve((size_t)std::max(n, 1)));
@@ -2597,9 +1885,6 @@ int owgs_read_concurrent(owgs_ctx* c, int32_t invoker, int32_t key, int32_t* per
     int2 v;
     HIPCHK(c, hipMemcpyAsync(&v, dv.p, sizeof(int2), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    di.release();
-    dk.release();
-    dv.release();
     if (v.x < 0) return 0;  // absent (NestedSemaphore.concurrentState has no entry); present entries may count <= 0
     if (permits) *permits = v.x;
     if (op_count) *op_count = v.y;
@@ -2671,7 +1956,6 @@ int owgs_pairwise_coprime(owgs_ctx* c, int32_t x, int32_t* out, int32_t cap, int
     if (out && cap > 0 && cnt > 0)
         HIPCHK(c, hipMemcpy(out, d.p + 2, (size_t)std::min(cap, cnt) * 4, hipMemcpyDeviceToHost));
     if (n) *n = cnt;
-    d.release();
     return OWGS_OK;
 }
 
@@ -2914,8 +2198,8 @@ static int spec_replay(owgs_ctx* c, int32_t nb, const int64_t* acq_off, const in
         a.s_claim = c->d_claim.p;
     }
     if (!c->ev_engine[0]) {
-        HIPCHK(c, hipEventCreate(&c->ev_engine[0]));
-        HIPCHK(c, hipEventCreate(&c->ev_engine[1]));
+        HIPCHK(c, c->ev_engine[0].create());
+        HIPCHK(c, c->ev_engine[1].create());
     }
     const size_t lds = owgs_resident_image_bytes(c->n_slots, c->n_ids) + (size_t)a.stage_bytes;
     HIPCHK(c, hipEventRecord(c->ev_engine[0], hs));
@@ -3103,17 +2387,11 @@ static int replay_device_multi_impl(owgs_ctx** cs, int32_t k, const owgs_replay_
         const size_t bytes = (size_t)k * sizeof(OwgsEngineArgs);
         // the previous multi launch of this leader (maybe on another stream) may still read both buffers
         if (c0->ev_margs_valid) HIPCHK(c0, hipEventSynchronize(c0->ev_margs));
-        if (c0->h_margs_bytes < bytes) {
-            if (c0->h_margs) (void)hipHostFree(c0->h_margs);
-            c0->h_margs = nullptr;
-            c0->h_margs_bytes = 0;
-            HIPCHK(c0, hipHostMalloc(&c0->h_margs, bytes, hipHostMallocDefault));
-            c0->h_margs_bytes = bytes;
-        }
-        if (!c0->ev_margs) HIPCHK(c0, hipEventCreateWithFlags(&c0->ev_margs, hipEventDisableTiming));
-        memcpy(c0->h_margs, A.data(), bytes);
+        if (c0->h_margs.bytes < bytes) HIPCHK(c0, c0->h_margs.reserve(bytes, hipHostMallocDefault));
+        if (!c0->ev_margs) HIPCHK(c0, c0->ev_margs.create(hipEventDisableTiming));
+        memcpy(c0->h_margs.p, A.data(), bytes);
         HIPCHK(c0, c0->d_margs.reserve((bytes + 3) / 4));
-        HIPCHK(c0, hipMemcpyAsync(c0->d_margs.p, c0->h_margs, bytes, hipMemcpyHostToDevice, hs));
+        HIPCHK(c0, hipMemcpyAsync(c0->d_margs.p, c0->h_margs.p, bytes, hipMemcpyHostToDevice, hs));
         HIPCHK(c0, c0->variant ? owgs_launch_engine_multi_dev_narrow(A.data(), (const OwgsEngineArgs*)c0->d_margs.p, k, hs)
                                : owgs_launch_engine_multi_dev(A.data(), (const OwgsEngineArgs*)c0->d_margs.p, k, hs));
         HIPCHK(c0, hipEventRecord(c0->ev_margs, hs));
@@ -3343,22 +2621,10 @@ int owgs_process_batch(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, cons
     const size_t in_bytes = al(o_sq + (seq ? 8 * (size_t)NP : 0));
     const size_t q_inv = 0, q_fl = al(4 * (size_t)NP), q_rf = al(q_fl + (size_t)NP), q_err = al(q_rf + (size_t)NR);
     const size_t out_bytes = q_err + 16;
-    if (c->h_pin_bytes < in_bytes) {
-        if (c->h_pin) (void)hipHostFree(c->h_pin);
-        c->h_pin = nullptr;
-        c->h_pin_bytes = 0;
-        HIPCHK(c, hipHostMalloc(&c->h_pin, in_bytes * 2, hipHostMallocDefault));
-        c->h_pin_bytes = in_bytes * 2;
-    }
-    if (c->h_pout_bytes < out_bytes) {
-        if (c->h_pout) (void)hipHostFree(c->h_pout);
-        c->h_pout = nullptr;
-        c->h_pout_bytes = 0;
-        HIPCHK(c, hipHostMalloc(&c->h_pout, out_bytes * 2, hipHostMallocDefault));
-        c->h_pout_bytes = out_bytes * 2;
-    }
+    if (c->h_pin.bytes < in_bytes) HIPCHK(c, c->h_pin.reserve(in_bytes * 2, hipHostMallocDefault));
+    if (c->h_pout.bytes < out_bytes) HIPCHK(c, c->h_pout.reserve(out_bytes * 2, hipHostMallocDefault));
     HIPCHK(c, hipStreamSynchronize(s));  // the previous call's copies out of the pinned buffers are done
-    char* H = (char*)c->h_pin;
+    char* H = (char*)c->h_pin.p;
     int64_t* h_acq = (int64_t*)(H + o_acq);
     int64_t* h_rel = (int64_t*)(H + o_rel);
     int64_t* h_run = (int64_t*)(H + o_run);
@@ -3450,20 +2716,20 @@ int owgs_process_batch(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, cons
         }
         // the context's error word after the launch: stored by the engine into the pinned output block (past the
         // range the copy below brings back), not copied after it
-        A.err_host = (int32_t*)((char*)c->h_pout + q_err);
+        A.err_host = (int32_t*)((char*)c->h_pout.p + q_err);
         // ... and its outputs: the engine's last step copies them there (no copy queued behind it)
         A.out_copy_src = (const uint4*)c->d_pout.p;
-        A.out_copy_dst = (uint4*)c->h_pout;
+        A.out_copy_dst = (uint4*)c->h_pout.p;
         A.out_copy_n16 = (int32_t)(q_err / 16);
         if (!rc) rc = run_engine(c, A, s);
     }
     if (rc) return rc;
     if (!fused) {
         HIPCHK(c, hipMemcpyAsync(c->d_pout.p + q_err, c->d_err.p, 4, hipMemcpyDeviceToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(c->h_pout, c->d_pout.p, out_bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(c->h_pout.p, c->d_pout.p, out_bytes, hipMemcpyDeviceToHost, s));
     }
     HIPCHK(c, hipStreamSynchronize(s));
-    const char* HO = (const char*)c->h_pout;
+    const char* HO = (const char*)c->h_pout.p;
     int32_t e = 0;
     memcpy(&e, HO + q_err, 4);
     if (fused && (e & OWGS_ERR_RELRISK)) {
@@ -3486,7 +2752,7 @@ int owgs_process_batch(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, cons
         rc = process_runs(c, n_runs, rel_off, pub_off, d_run, d_pa, d_ri, d_ra, d_sq, seq_base, d_out, d_fl, d_rf, s);
         if (rc) return rc;
         HIPCHK(c, hipMemcpyAsync(c->d_pout.p + q_err, c->d_err.p, 4, hipMemcpyDeviceToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(c->h_pout, c->d_pout.p, out_bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(c->h_pout.p, c->d_pout.p, out_bytes, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         memcpy(&e, HO + q_err, 4);
     }
@@ -3502,7 +2768,7 @@ int owgs_process_batch(owgs_ctx* c, int32_t n_runs, const int32_t* rel_off, cons
     // host returns instead of the next small call paying the launch and the load.  Only here, after this call's
     // stream has drained: an operation queued behind the engine on a hardware queue the streams share would wait for
     // its idle exit
-    if (relaunch && res_eligible(c, 1, 0, 1, false) && c->res_in && c->res_out && !c->res_alive) {
+    if (relaunch && res_eligible(c, 1, 0, 1, false) && c->res_in.p && c->res_out.p && !c->res_alive) {
         const int rl = res_launch(c);
         if (rl) return rl;
     }
@@ -3617,7 +2883,7 @@ static int update_health_device_impl(owgs_ctx* c, int32_t n, const uint8_t* stat
         hipStream_t s = stream ? (hipStream_t)stream : c->stream;
         HIPCHK(c, hipMemcpyAsync(c->d_status.p, status_dev, (size_t)n, hipMemcpyDeviceToDevice, s));
         HIPCHK(c, owgs_launch_usable(c->d_status.p, n, c->d_usable.p, (n + 31) / 32 + 1, s));
-        if (!c->ev_status) HIPCHK(c, hipEventCreateWithFlags(&c->ev_status, hipEventDisableTiming));
+        if (!c->ev_status) HIPCHK(c, c->ev_status.create(hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(c->ev_status, s));
         c->status_stale = true;
         return OWGS_OK;
@@ -3684,803 +2950,6 @@ int owgs_read_stats(owgs_ctx* c, uint64_t* out, int32_t cap) {
     return OWGS_OK;
 }
 
-}  // extern "C"
-
-// ============================================================================================== completion acks
-// activationSlots (CLB:60) on the device; see owgs_acks.hip.
-
-static OwgsActTable act_table(owgs_ctx* c) {
-    OwgsActTable T;
-    T.tw = c->t_tw.p;
-    T.tk = c->t_tk.p;
-    T.tv = c->t_tv.p;
-    T.tn = c->t_tn.p;
-    T.owner = c->t_owner.p;
-    T.cap = c->t_cap;
-    T.td = c->t_td.p;
-    T.ti = c->t_ti.p;
-    T.tq = c->t_tq.p;
-    T.tmin = c->t_tmin.p;
-    return T;
-}
-
-// keep used slots (live + deleted) under half the capacity: rehash the live entries into a table of
-// max(cap, 4 * (live + n)) slots when n more inserts could cross it
-static int act_reserve(owgs_ctx* c, long long n) {
-    if (c->t_cap > 0 && c->t_used + n <= c->t_cap / 2) return OWGS_OK;
-    long long cap = 1 << 16;
-    while (cap < 4 * (c->t_live + n)) cap <<= 1;
-    if (cap < c->t_cap) cap = c->t_cap;
-    DevBuf<unsigned long long> tw;
-    DevBuf<ulonglong2> tk;
-    DevBuf<int2> tv;
-    DevBuf<int32_t> tn, ow, ti;
-    DevBuf<long long> td, tmin;
-    DevBuf<unsigned long long> tq;
-    HIPCHK(c, td.reserve((size_t)cap));
-    HIPCHK(c, ti.reserve((size_t)cap));
-    HIPCHK(c, tq.reserve((size_t)cap));
-    HIPCHK(c, tmin.reserve((size_t)(cap >> OWGS_TILE_LOG2)));
-    HIPCHK(c, tw.reserve((size_t)cap));
-    HIPCHK(c, tk.reserve((size_t)cap));
-    HIPCHK(c, tv.reserve((size_t)cap));
-    HIPCHK(c, tn.reserve((size_t)cap));
-    HIPCHK(c, ow.reserve((size_t)cap));
-    OwgsActTable T{tw.p, tk.p, tv.p, tn.p, ow.p, cap, td.p, ti.p, tq.p, tmin.p};
-    HIPCHK(c, owgs_launch_act_init(&T, c->stream));
-    if (c->t_cap > 0) {
-        OwgsActTable O = act_table(c);
-        HIPCHK(c, owgs_launch_act_rehash(&O, &T, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->t_tw.release();
-    c->t_tk.release();
-    c->t_tv.release();
-    c->t_tn.release();
-    c->t_owner.release();
-    c->t_td.release();
-    c->t_ti.release();
-    c->t_tq.release();
-    c->t_tmin.release();
-    c->t_td = td;
-    c->t_ti = ti;
-    c->t_tq = tq;
-    c->t_tmin = tmin;
-    td.p = nullptr;
-    ti.p = nullptr;
-    tq.p = nullptr;
-    tmin.p = nullptr;
-    c->t_tw = tw;
-    c->t_tk = tk;
-    c->t_tv = tv;
-    c->t_tn = tn;
-    c->t_owner = ow;
-    tw.p = nullptr;
-    tk.p = nullptr;
-    tv.p = nullptr;
-    tn.p = nullptr;
-    ow.p = nullptr;
-    c->t_cap = cap;
-    c->t_used = c->t_live;
-    return OWGS_OK;
-}
-
-int owgs_set_health_tid(owgs_ctx* c, int64_t start_ms) {
-    if (!c) return OWGS_EINVAL;
-    c->health_ms = start_ms;
-    return OWGS_OK;
-}
-
-int owgs_activations_live(owgs_ctx* c, int64_t* live) {
-    if (!c || !live) return OWGS_EINVAL;
-    *live = c->t_live;
-    return OWGS_OK;
-}
-
-static OwgsInflight inflight_args(owgs_ctx* c) {
-    OwgsInflight F;
-    F.active = c->d_ns_active.p;
-    F.act_mem = c->d_act_mem.p;
-    F.act_bb = c->d_act_bb.p;
-    return F;
-}
-
-// The device half of setupActivation (CLB:116-166) over device arrays: claim / fill / publish for n ids with their
-// action, namespace (null: none), ticket, entry invoker and time limit (inv null: an untimed call, nothing armed),
-// shared by the track entry points and owgs_publish_activations.  placed (null: every item) is the latter's predicate:
-// an item it clears touches neither the table nor a counter and keeps the out_ticket / out_existed already there.
-// The caller has run act_reserve(c, n) and zeroed counters; queued on st, no wait.  The arm counter advances by n.
-static int track_device(owgs_ctx* c, int32_t n, const ulonglong2* key, const int32_t* action, const int32_t* ns,
-                        const int32_t* ticket, const int32_t* inv, const long long* tl, int64_t now_ms,
-                        const uint8_t* placed, int32_t* out_ticket, uint8_t* out_existed,
-                        unsigned long long* counters, hipStream_t st) {
-    HIPCHK(c, c->k_slot.reserve((size_t)n));
-    HIPCHK(c, c->k_state.reserve((size_t)n));
-    OwgsArm arm{};
-    arm.seq_base = c->arm_seq;
-    if (inv) {
-        arm.inv = inv;
-        arm.tl = tl;
-        arm.now = now_ms;
-        arm.std_ms = c->a_std;
-        arm.factor = c->a_factor;
-        arm.addon = c->a_addon;
-    }
-    OwgsActTable T = act_table(c);
-    const OwgsInflight F = inflight_args(c);
-    HIPCHK(c, owgs_launch_act_track(&T, key, n, action, ns, ticket, c->k_slot.p, c->k_state.p, out_ticket,
-                                    out_existed, counters, &F, &arm, placed, st));
-    c->arm_seq += (unsigned long long)n;  // arm order = track call order, then array index
-    return OWGS_OK;
-}
-
-// ns = null: every item without a namespace (owgs_track_activations); invoker = null: nothing armed (the untimed calls)
-static int track_impl(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* action, const int32_t* ns,
-                      const int32_t* ticket, int32_t* out_ticket, uint8_t* out_existed,
-                      const int32_t* invoker = nullptr, const int64_t* time_limit_ms = nullptr, int64_t now_ms = 0) {
-    if (!c || n < 0 || (n > 0 && (!aid32 || !action || !ticket || !out_ticket || !out_existed))) return OWGS_EINVAL;
-    if (n == 0) return OWGS_OK;
-    if (invoker) {
-        if (now_ms < 0 || now_ms >= (1LL << 60)) return c->fail(OWGS_EINVAL, "track: now outside [0, 2^60)");
-        for (int32_t i = 0; i < n; ++i)
-            if (invoker[i] < 0 || time_limit_ms[i] < 0 || time_limit_ms[i] >= (1LL << 40))
-                return c->fail(OWGS_EINVAL, "track: negative invoker or time limit outside [0, 2^40)");
-    }
-    if (!registered(c, n, action)) return c->fail(OWGS_ENOENT, "unknown action");
-    if (ns) {
-        const int32_t nn = (int32_t)c->ns_map.size();
-        for (int32_t i = 0; i < n; ++i)
-            if (ns[i] != OWGS_NONE && (ns[i] < 0 || ns[i] >= nn)) return c->fail(OWGS_ENOENT, "unknown namespace");
-    }
-    // ActivationId.asString is 32 chars of [0-9a-f]; reject a malformed batch before any entry is created
-    for (size_t k = 0; k < (size_t)n * 32; ++k) {
-        const char ch = aid32[k];
-        if (!((ch >= '0' && ch <= '9') || (ch >= 'a' && ch <= 'f')))
-            return c->fail(OWGS_EINVAL, "activation id is not 32 characters of [0-9a-f]");
-    }
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    int rc = act_reserve(c, n);
-    if (rc) return rc;
-    HIPCHK(c, upload(c->k_aid, aid32, (size_t)n * 32, c->stream));
-    HIPCHK(c, upload(c->k_act, action, (size_t)n, c->stream));
-    HIPCHK(c, upload(c->k_r0, ticket, (size_t)n, c->stream));
-    HIPCHK(c, c->k_key.reserve((size_t)n));
-    HIPCHK(c, c->k_tick.reserve((size_t)n));
-    HIPCHK(c, c->k_oflags.reserve((size_t)n));
-    if (ns) HIPCHK(c, upload(c->k_r1, ns, (size_t)n, c->stream));
-    if (invoker) {
-        HIPCHK(c, upload(c->x_inv, invoker, (size_t)n, c->stream));
-        HIPCHK(c, upload(c->x_tl, (const long long*)time_limit_ms, (size_t)n, c->stream));
-    }
-    HIPCHK(c, c->k_cnt.reserve(OWGS_CNT_WORDS));
-    HIPCHK(c, hipMemsetAsync(c->k_cnt.p, 0, OWGS_CNT_WORDS * 8, c->stream));
-    HIPCHK(c, owgs_launch_aid_decode(c->k_aid.p, n, nullptr, c->k_key.p, nullptr, nullptr, nullptr, c->stream));
-    rc = track_device(c, n, c->k_key.p, c->k_act.p, ns ? c->k_r1.p : nullptr, c->k_r0.p,
-                      invoker ? c->x_inv.p : nullptr, invoker ? c->x_tl.p : nullptr, now_ms, nullptr, c->k_tick.p,
-                      c->k_oflags.p, c->k_cnt.p, c->stream);
-    if (rc) return rc;
-    unsigned long long cnt[OWGS_CNT_WORDS];
-    HIPCHK(c, hipMemcpyAsync(out_ticket, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out_existed, c->k_oflags.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cnt, c->k_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->t_used += (long long)cnt[OWGS_CNT_INSERTED];
-    c->t_live += (long long)cnt[OWGS_CNT_INSERTED];
-    // CLB:121-125 for every item of the batch, duplicates included (they run before getOrElseUpdate, CLB:148)
-    c->f_total += n;
-    c->f_mb_managed += (long long)cnt[OWGS_CNT_MANAGED_MB];
-    c->f_mb_blackbox += (long long)cnt[OWGS_CNT_BLACKBOX_MB];
-    for (int32_t i = 0; i < n; ++i)
-        if (out_existed[i] == 2) return c->fail(OWGS_EINVAL, "activation id is not 32 characters of [0-9a-f]");
-    return OWGS_OK;
-}
-
-int owgs_track_activations(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* action, const int32_t* ticket,
-                           int32_t* out_ticket, uint8_t* out_existed) {
-    return track_impl(c, n, aid32, action, nullptr, ticket, out_ticket, out_existed);
-}
-
-int owgs_track_activations_ns(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* action, const int32_t* ns,
-                              const int32_t* ticket, int32_t* out_ticket, uint8_t* out_existed) {
-    if (n > 0 && !ns) return OWGS_EINVAL;
-    return track_impl(c, n, aid32, action, ns, ticket, out_ticket, out_existed);
-}
-
-int owgs_set_ack_timeout(owgs_ctx* c, int64_t std_ms, int32_t factor, int64_t addon_ms) {
-    if (!c) return OWGS_EINVAL;
-    if (std_ms < 0 || std_ms >= (1LL << 40) || addon_ms < 0 || addon_ms >= (1LL << 40) || factor < 1 ||
-        factor >= (1 << 16))
-        return c->fail(OWGS_EINVAL, "ack timeout: std / addon outside [0, 2^40) or factor outside [1, 2^16)");
-    c->a_std = std_ms;
-    c->a_factor = factor;
-    c->a_addon = addon_ms;
-    return OWGS_OK;
-}
-
-int owgs_track_activations_timed(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* action, const int32_t* ns,
-                                 const int32_t* ticket, const int32_t* invoker, const int64_t* time_limit_ms,
-                                 int64_t now_ms, int32_t* out_ticket, uint8_t* out_existed) {
-    if (n > 0 && (!invoker || !time_limit_ms)) return OWGS_EINVAL;
-    return track_impl(c, n, aid32, action, ns, ticket, out_ticket, out_existed, invoker, time_limit_ms, now_ms);
-}
-
-// the completion's share of the books (CLB:280-284): one decrement per removed entry, the entries' megabytes
-static void inflight_release(owgs_ctx* c, const unsigned long long* cnt) {
-    c->f_total -= (long long)cnt[OWGS_CNT_REMOVED];
-    c->f_mb_managed -= (long long)cnt[OWGS_CNT_MANAGED_MB];
-    c->f_mb_blackbox -= (long long)cnt[OWGS_CNT_BLACKBOX_MB];
-}
-
-// owgs_process_result_acks' share of the tail: result-only records look their entry up, the flags kernel adds the result
-// bits and the ids, and the output block's copy is queued before the tail's one synchronisation
-struct AckResultTail {
-    unsigned long long* d_aid;  // [2n] in the block
-    void* pin;                  // pinned destination
-    const void* blk;            // the block
-    size_t bytes;
-};
-
-// shared tail: info/key/inst of n messages are in k_info/k_key/k_inst; resolve, release in order, flags
-static int ack_complete(owgs_ctx* c, int32_t n, uint8_t* d_kind, int32_t* d_ticket, uint8_t* d_flags,
-                        hipStream_t st, const AckResultTail* rt = nullptr) {
-    if (c->t_cap == 0) {
-        int rc = act_reserve(c, 0);
-        if (rc) return rc;
-    }
-    HIPCHK(c, c->k_slot.reserve((size_t)n));
-    HIPCHK(c, c->k_r0.reserve((size_t)n));
-    HIPCHK(c, c->k_r1.reserve((size_t)n));
-    HIPCHK(c, c->k_r2.reserve((size_t)n));
-    HIPCHK(c, c->k_r3.reserve((size_t)n));
-    HIPCHK(c, c->d_rflags.reserve((size_t)n));
-    HIPCHK(c, c->k_cnt.reserve(OWGS_CNT_WORDS));
-    HIPCHK(c, hipMemsetAsync(c->k_cnt.p, 0, OWGS_CNT_WORDS * 8, st));
-    if (!c->d_act_mem.p) {  // no actions registered: every lookup misses, the records are never read
-        HIPCHK(c, c->d_act_mem.reserve(1));
-        HIPCHK(c, c->d_act_maxc.reserve(1));
-        HIPCHK(c, c->d_act_slot.reserve(1));
-        HIPCHK(c, c->d_act_bb.reserve(1));
-    }
-    OwgsActTable T = act_table(c);
-    OwgsAckCompleteArgs a{};
-    a.key = c->k_key.p;
-    a.info = c->k_info.p;
-    a.inst = c->k_inst.p;
-    a.n = n;
-    a.slot = c->k_slot.p;
-    a.act_mem = c->d_act_mem.p;
-    a.act_maxc = c->d_act_maxc.p;
-    a.act_slot = c->d_act_slot.p;
-    a.n_slots = c->n_slots;
-    a.r_inv = c->k_r0.p;
-    a.r_mem = c->k_r1.p;
-    a.r_maxc = c->k_r2.p;
-    a.r_slot = c->k_r3.p;
-    a.out_kind = d_kind;
-    a.out_ticket = d_ticket;
-    a.counters = c->k_cnt.p;
-    a.fl = inflight_args(c);
-    a.results = rt ? 1 : 0;
-    HIPCHK(c, owgs_launch_ack_complete(&T, &a, st));
-    if (c->large) {  // the large-state engine applies the records in message order (owgs_seq.hip)
-        const int64_t offs[4] = {0, (int64_t)n, 0, 0};
-        HIPCHK(c, upload(c->g_off, offs, 4, st));
-        OwgsSeqArgs S = seq_args(c);
-        S.n_runs = 1;
-        S.rel_off = c->g_off.p;
-        S.pub_off = c->g_off.p + 2;
-        S.rel_inv = c->k_r0.p;
-        S.rel_mem = c->k_r1.p;
-        S.rel_maxc = c->k_r2.p;
-        S.rel_slot = c->k_r3.p;
-        S.rel_flags = c->d_rflags.p;
-        int rs = seq_run(c, S, st);
-        if (rs) return rs;
-        HIPCHK(c, owgs_launch_ack_flags(n, c->k_info.p, c->d_rflags.p, d_kind, d_flags, c->k_key.p,
-                                        rt ? rt->d_aid : nullptr, st));
-        if (rt) HIPCHK(c, hipMemcpyAsync(rt->pin, rt->blk, rt->bytes, hipMemcpyDeviceToHost, st));
-        unsigned long long cnt[OWGS_CNT_WORDS];
-        HIPCHK(c, hipMemcpyAsync(cnt, c->k_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        c->t_live -= (long long)cnt[OWGS_CNT_REMOVED];
-        inflight_release(c, cnt);
-        return check_err_word(c);
-    }
-    OwgsReleaseArgs R{};
-    R.permits = c->d_permits.p;
-    R.n_slots = c->n_slots;
-    R.ct_keys = c->d_ct_keys.p;
-    R.ct_vals = c->d_ct_vals.p;
-    R.ovf = ovf_args(c);
-    R.n = n;
-    R.inv = c->k_r0.p;
-    R.mem = c->k_r1.p;
-    R.maxc = c->k_r2.p;
-    R.slot = c->k_r3.p;
-    R.flags = c->d_rflags.p;
-    R.err = c->d_err.p;
-    int rs = release_scratch(c, R, n);
-    if (!rs && c->w_cap > 0) {
-        rs = ensure_ovf(c, n, st);
-        ovf_add(c, n);
-    }
-    if (rs) return rs;
-    R.ovf = ovf_args(c);
-    R.w = watch_args(c);
-    HIPCHK(c, owgs_launch_release_seq(&R, st));
-    HIPCHK(c, owgs_launch_ack_flags(n, c->k_info.p, c->d_rflags.p, d_kind, d_flags, c->k_key.p,
-                                    rt ? rt->d_aid : nullptr, st));
-    if (rt) HIPCHK(c, hipMemcpyAsync(rt->pin, rt->blk, rt->bytes, hipMemcpyDeviceToHost, st));
-    unsigned long long cnt[OWGS_CNT_WORDS];
-    HIPCHK(c, hipMemcpyAsync(cnt, c->k_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    c->t_live -= (long long)cnt[OWGS_CNT_REMOVED];
-    inflight_release(c, cnt);
-    rs = w_refresh(c, st);
-    return rs ? rs : check_err_word(c);
-}
-
-int owgs_process_acks_device(owgs_ctx* c, int32_t n, const uint8_t* bytes, const int64_t* off, uint8_t* out_kind,
-                             int32_t* out_invoker, int32_t* out_ticket, uint8_t* out_flags, void* stream) {
-    if (!c || n < 0 || (n > 0 && (!bytes || !off || !out_kind || !out_invoker || !out_ticket || !out_flags)))
-        return OWGS_EINVAL;
-    if (n == 0) return OWGS_OK;
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, stream ? (hipStream_t)stream : c->stream);
-        if (ro_) return ro_;
-    }
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, c->k_key.reserve((size_t)n));
-    HIPCHK(c, c->k_info.reserve((size_t)n));
-    OwgsAckParseArgs p{};
-    p.bytes = bytes;
-    p.off = off;
-    p.n = n;
-    p.health_start_ms = c->health_ms;
-    p.forced = nullptr;
-    p.key = c->k_key.p;
-    p.inst = out_invoker;
-    p.info = c->k_info.p;
-    HIPCHK(c, owgs_launch_ack_parse(&p, st));
-    // the resolve step reads the instance from k_inst
-    HIPCHK(c, c->k_inst.reserve((size_t)n));
-    HIPCHK(c, hipMemcpyAsync(c->k_inst.p, out_invoker, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    return ack_complete(c, n, out_kind, out_ticket, out_flags, st);
-}
-
-int owgs_process_acks(owgs_ctx* c, int32_t n, const char* bytes, const int64_t* off, uint8_t* out_kind,
-                      int32_t* out_invoker, int32_t* out_ticket, uint8_t* out_flags) {
-    if (!c || n < 0 || (n > 0 && (!bytes || !off || !out_kind || !out_invoker || !out_ticket || !out_flags)))
-        return OWGS_EINVAL;
-    if (n == 0) return OWGS_OK;
-    for (int32_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i] || off[i] < 0) return c->fail(OWGS_EINVAL, "offsets");
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    const size_t nb = (size_t)(off[n] - off[0]);
-    std::vector<int64_t> o((size_t)n + 1);
-    for (int32_t i = 0; i <= n; ++i) o[i] = off[i] - off[0];
-    HIPCHK(c, c->k_bytes.reserve(nb + 32));
-    HIPCHK(c, hipMemsetAsync(c->k_bytes.p + nb, 0, 32, c->stream));
-    if (nb) HIPCHK(c, hipMemcpyAsync(c->k_bytes.p, bytes + off[0], nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, upload(c->k_off, o.data(), o.size(), c->stream));
-    HIPCHK(c, c->k_kind.reserve((size_t)n));
-    HIPCHK(c, c->k_tick.reserve((size_t)n));
-    HIPCHK(c, c->k_oflags.reserve((size_t)n));
-    HIPCHK(c, c->k_act.reserve((size_t)n));
-    int rc = owgs_process_acks_device(c, n, c->k_bytes.p, c->k_off.p, c->k_kind.p, c->k_act.p, c->k_tick.p,
-                                      c->k_oflags.p, nullptr);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpy(out_kind, c->k_kind.p, (size_t)n, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_invoker, c->k_act.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_ticket, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_flags, c->k_oflags.p, (size_t)n, hipMemcpyDeviceToHost));
-    return OWGS_OK;
-}
-
-int owgs_complete_activations(owgs_ctx* c, int32_t n, const char* aid32, const int32_t* invoker, const uint8_t* flags,
-                              uint8_t* out_kind, int32_t* out_ticket, uint8_t* out_flags) {
-    if (!c || n < 0 || (n > 0 && (!aid32 || !invoker || !flags || !out_kind || !out_ticket || !out_flags)))
-        return OWGS_EINVAL;
-    if (n == 0) return OWGS_OK;
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    HIPCHK(c, upload(c->k_aid, aid32, (size_t)n * 32, c->stream));
-    HIPCHK(c, upload(c->k_cfl, flags, (size_t)n, c->stream));
-    HIPCHK(c, upload(c->k_act, invoker, (size_t)n, c->stream));
-    HIPCHK(c, c->k_key.reserve((size_t)n));
-    HIPCHK(c, c->k_info.reserve((size_t)n));
-    HIPCHK(c, c->k_inst.reserve((size_t)n));
-    HIPCHK(c, c->k_kind.reserve((size_t)n));
-    HIPCHK(c, c->k_tick.reserve((size_t)n));
-    HIPCHK(c, c->k_oflags.reserve((size_t)n));
-    HIPCHK(c, owgs_launch_aid_decode(c->k_aid.p, n, c->k_cfl.p, c->k_key.p, c->k_info.p, c->k_inst.p, c->k_act.p,
-                                     c->stream));
-    int rc = ack_complete(c, n, c->k_kind.p, c->k_tick.p, c->k_oflags.p, c->stream);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpy(out_kind, c->k_kind.p, (size_t)n, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_ticket, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_flags, c->k_oflags.p, (size_t)n, hipMemcpyDeviceToHost));
-    return OWGS_OK;
-}
-
-// ------------------------------------------------------------------------------------------ completion-ack timeouts
-// owgs_expire.hip finds and orders the due entries; the removal, the books and releaseInvoker are ack_complete's.
-int owgs_expire_activations(owgs_ctx* c, int64_t now_ms, int32_t cap, int32_t feed_health, int32_t* out_n,
-                            int64_t* out_remaining, uint64_t* out_aid, int32_t* out_ticket, int32_t* out_invoker,
-                            int64_t* out_deadline, uint8_t* out_flags) {
-    if (!c || !out_n || !out_remaining || cap < 0 ||
-        (cap > 0 && (!out_aid || !out_ticket || !out_invoker || !out_deadline || !out_flags)))
-        return OWGS_EINVAL;
-    if (now_ms < 0 || now_ms >= (1LL << 60)) return c->fail(OWGS_EINVAL, "expire: now outside [0, 2^60)");
-    if (feed_health && now_ms < c->h_now)
-        return c->fail(OWGS_EINVAL, "expire: now before the health supervision's last batch");
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    hipStream_t st = c->stream;
-    if (c->t_cap == 0) {
-        int rc = act_reserve(c, 0);
-        if (rc) return rc;
-    }
-    // every buffer the sweep needs before its first kernel: the scan rewrites the summary words of the tiles it reads
-    // and the emit step completes them, so nothing between the two may fail for want of memory
-    const size_t live = (size_t)std::max<long long>(c->t_live, 1);
-    const size_t tb = owgs_expire_sort_bytes((int32_t)live);
-    HIPCHK(c, c->x_cnt.reserve(2));
-    HIPCHK(c, c->x_d.reserve(live));
-    HIPCHK(c, c->x_q.reserve(live));
-    HIPCHK(c, c->x_slot.reserve(live));
-    HIPCHK(c, c->x_idx0.reserve(live));
-    HIPCHK(c, c->x_idx1.reserve(live));
-    HIPCHK(c, c->x_key.reserve(live));
-    HIPCHK(c, c->x_key_s.reserve(live));
-    HIPCHK(c, c->x_outd.reserve(live));
-    HIPCHK(c, c->x_temp.reserve(tb));
-    HIPCHK(c, c->k_key.reserve(live));
-    HIPCHK(c, c->k_inst.reserve(live));
-    HIPCHK(c, c->k_info.reserve(live));
-    HIPCHK(c, c->k_kind.reserve(live));
-    HIPCHK(c, c->k_tick.reserve(live));
-    HIPCHK(c, c->k_oflags.reserve(live));
-    OwgsExpireArgs a{};
-    a.T = act_table(c);
-    a.now = now_ms;
-    a.cnt = c->x_cnt.p;
-    a.due_cap = (int32_t)live;
-    a.due_d = c->x_d.p;
-    a.due_q = c->x_q.p;
-    a.due_slot = c->x_slot.p;
-    HIPCHK(c, hipMemsetAsync(c->x_cnt.p, 0, 2 * sizeof(int32_t), st));
-    HIPCHK(c, owgs_launch_expire_scan(&a, st));
-    int32_t cnt[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(cnt, c->x_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    c->x_sweeps += 1;
-    c->x_tiles += cnt[1];
-    c->x_tiles_last = cnt[1];
-    const int32_t due = cnt[0];
-    if ((long long)due > c->t_live) return c->fail(OWGS_EDEVICE, "expire: more due entries than live ones");
-    const int32_t take = std::min(due, cap);
-    *out_n = take;
-    *out_remaining = (int64_t)due - take;
-    if (due == 0) return OWGS_OK;
-    int32_t seq_bits = 1;
-    while (seq_bits < 64 && (c->arm_seq >> seq_bits) != 0) ++seq_bits;
-    HIPCHK(c, owgs_launch_expire_order(&a, due, take, seq_bits, c->x_temp.p, tb, c->x_idx0.p, c->x_idx1.p, c->x_key.p,
-                                       c->x_key_s.p, c->k_key.p, c->k_inst.p, c->k_info.p, c->x_outd.p, st));
-    if (take == 0) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        return OWGS_OK;
-    }
-    // processCompletion(aid, tid, forced = true, isSystemError = false, invoker = entry.invoker) for each, in order
-    int rc = ack_complete(c, take, c->k_kind.p, c->k_tick.p, c->k_oflags.p, st);
-    if (rc) return rc;
-    c->x_expired += take;
-    HIPCHK(c, hipMemcpy(out_aid, c->k_key.p, (size_t)take * 16, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_ticket, c->k_tick.p, (size_t)take * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_invoker, c->k_inst.p, (size_t)take * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_deadline, c->x_outd.p, (size_t)take * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_flags, c->k_oflags.p, (size_t)take, hipMemcpyDeviceToHost));
-    if (!feed_health) return OWGS_OK;
-    // InvocationFinishedMessage(invoker, Timeout) of each expired entry (CLB:317) in the same order; ids the status
-    // vector cannot hold were never registered, and the pool ignores a message for an unregistered invoker
-    std::vector<int32_t> inv;
-    inv.reserve((size_t)take);
-    for (int32_t i = 0; i < take; ++i)
-        if (out_invoker[i] >= 0 && out_invoker[i] < OWGS_HEALTH_MAX_ID) inv.push_back(out_invoker[i]);
-    if (inv.empty()) return OWGS_OK;
-    const std::vector<uint8_t> kind(inv.size(), (uint8_t)OWGS_EV_TIMEOUT);
-    const std::vector<int64_t> t(inv.size(), now_ms), mem(inv.size(), 0);
-    return owgs_health_events(c, (int32_t)inv.size(), inv.data(), kind.data(), t.data(), mem.data(), now_ms, 0);
-}
-
-int owgs_next_deadline(owgs_ctx* c, int64_t* t_ms) {
-    if (!c || !t_ms) return OWGS_EINVAL;
-    *t_ms = INT64_MAX;
-    if (c->t_cap == 0) return OWGS_OK;
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    HIPCHK(c, c->x_outd.reserve(1));
-    const OwgsActTable T = act_table(c);
-    HIPCHK(c, owgs_launch_deadline_min(&T, c->x_outd.p, c->stream));
-    long long v = 0;
-    HIPCHK(c, hipMemcpyAsync(&v, c->x_outd.p, sizeof(v), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *t_ms = (int64_t)v;
-    return OWGS_OK;
-}
-
-int owgs_expiry_stats(owgs_ctx* c, int64_t out[5]) {
-    if (!c || !out) return OWGS_EINVAL;
-    out[0] = c->x_sweeps;
-    out[1] = c->x_tiles;
-    out[2] = c->x_tiles_last;
-    out[3] = c->x_expired;
-    out[4] = c->t_cap >> OWGS_TILE_LOG2;
-    return OWGS_OK;
-}
-
-// ------------------------------------------------------------------------------------------ in-flight books
-// activationsPerNamespace (CLB:62) on the device, the three totals (CLB:63-65) on the host; see owgs_acks.hip for the
-// counting and owgs_inflight.hip for the reads and the throttle check.
-int owgs_register_namespaces(owgs_ctx* c, int32_t n, const uint64_t* uuid128, int32_t* out_ns) {
-    if (!c || n < 0 || (n > 0 && (!uuid128 || !out_ns))) return OWGS_EINVAL;
-    if (n == 0) return OWGS_OK;
-    // handles of the call: a uuid already registered (before or earlier in this call) keeps its handle
-    std::map<std::pair<uint64_t, uint64_t>, int32_t> fresh;
-    const int64_t have = (int64_t)c->ns_map.size();
-    for (int32_t i = 0; i < n; ++i) {
-        const std::pair<uint64_t, uint64_t> u(uuid128[2 * (size_t)i], uuid128[2 * (size_t)i + 1]);
-        if (!c->ns_map.count(u) && !fresh.count(u)) {
-            const int32_t h = (int32_t)(have + (int64_t)fresh.size());
-            fresh[u] = h;
-        }
-    }
-    const int64_t need = have + (int64_t)fresh.size();
-    if (need > (1 << 30)) return c->fail(OWGS_ERANGE, "more than 2^30 namespaces");
-    if (need > c->ns_cap) {  // grow geometrically on the context's stream; the old counters are copied, the rest zero
-        OWGS_ENTER(c);
-        {
-            const int ro_ = order_on(c, c->stream);
-            if (ro_) return ro_;
-        }
-        int64_t cap = std::max<int64_t>(c->ns_cap, OWGS_NS_INITIAL_CAP);
-        while (cap < need) cap *= 2;
-        DevBuf<int32_t> nb, rc;
-        DevBuf<long long> rm;  // the rate records grow with the counters: old records copied, new handles absent
-        hipError_t e = nb.reserve((size_t)cap);
-        if (e == hipSuccess) e = rm.reserve(2 * (size_t)cap);
-        if (e == hipSuccess) e = rc.reserve(2 * (size_t)cap);
-        if (e == hipSuccess) e = hipMemsetAsync(nb.p, 0, (size_t)cap * 4, c->stream);
-        if (e == hipSuccess && c->ns_cap > 0)
-            e = hipMemcpyAsync(nb.p, c->d_ns_active.p, (size_t)c->ns_cap * 4, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess)
-            e = owgs_launch_rate_grow(c->d_rate_min.p, c->d_rate_cnt.p, c->ns_cap, rm.p, rc.p, (int32_t)cap, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (the old arrays are freed below)
-        if (e != hipSuccess) {
-            nb.release();
-            rm.release();
-            rc.release();
-            return c->fail(OWGS_EDEVICE, "namespace counters", e);
-        }
-        c->d_ns_active.release();
-        c->d_ns_active = nb;
-        c->d_rate_min.release();
-        c->d_rate_min = rm;
-        c->d_rate_cnt.release();
-        c->d_rate_cnt = rc;
-        c->ns_cap = (int32_t)cap;
-    }
-    for (const auto& kv : fresh) c->ns_map[kv.first] = kv.second;
-    for (int32_t i = 0; i < n; ++i)
-        out_ns[i] = c->ns_map[std::make_pair(uuid128[2 * (size_t)i], uuid128[2 * (size_t)i + 1])];
-    return OWGS_OK;
-}
-
-static bool ns_known(const owgs_ctx* c, int32_t n, const int32_t* ns) {
-    const int32_t nn = (int32_t)c->ns_map.size();
-    for (int32_t i = 0; i < n; ++i)
-        if (ns[i] < 0 || ns[i] >= nn) return false;
-    return true;
-}
-
-int owgs_active_activations(owgs_ctx* c, int32_t n, const int32_t* ns, int32_t* out) {
-    if (!c || n < 0 || (n > 0 && (!ns || !out))) return OWGS_EINVAL;
-    if (n == 0) return OWGS_OK;
-    if (!ns_known(c, n, ns)) return c->fail(OWGS_ENOENT, "unknown namespace");
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    HIPCHK(c, upload(c->k_act, ns, (size_t)n, c->stream));
-    HIPCHK(c, c->k_tick.reserve((size_t)n));
-    HIPCHK(c, owgs_launch_ns_gather(c->d_ns_active.p, c->k_act.p, n, c->k_tick.p, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return OWGS_OK;
-}
-
-// (every call that moves the totals ends with a synchronisation and folds its words in there: the host values are
-// ordered after all earlier calls)
-int owgs_activation_totals(owgs_ctx* c, int64_t out[3]) {
-    if (!c || !out) return OWGS_EINVAL;
-    out[0] = c->f_total;
-    out[1] = c->f_mb_managed;
-    out[2] = c->f_mb_blackbox;
-    return OWGS_OK;
-}
-
-int owgs_throttle_batch(owgs_ctx* c, int32_t n, const int32_t* ns, const int32_t* limit, int32_t* out_count,
-                        uint8_t* out_ok) {
-    if (!c || n < 0 || (n > 0 && (!ns || !limit || !out_count || !out_ok))) return OWGS_EINVAL;
-    if (n == 0) return OWGS_OK;
-    for (int32_t i = 0; i < n; ++i)
-        if (ns[i] == OWGS_NONE) return c->fail(OWGS_EINVAL, "throttle check without a namespace");
-    if (!ns_known(c, n, ns)) return c->fail(OWGS_ENOENT, "unknown namespace");
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    int32_t bits = 1;
-    while (((int64_t)1 << bits) < (int64_t)c->ns_map.size()) ++bits;
-    const size_t tb = owgs_throttle_sort_bytes(n, bits);
-    HIPCHK(c, c->q_temp.reserve(tb));
-    HIPCHK(c, c->q_key.reserve((size_t)n));
-    HIPCHK(c, c->q_idx0.reserve((size_t)n));
-    HIPCHK(c, c->q_idx1.reserve((size_t)n));
-    HIPCHK(c, upload(c->k_act, ns, (size_t)n, c->stream));
-    HIPCHK(c, upload(c->k_r0, limit, (size_t)n, c->stream));
-    HIPCHK(c, c->k_tick.reserve((size_t)n));
-    HIPCHK(c, c->k_oflags.reserve((size_t)n));
-    HIPCHK(c, owgs_launch_throttle(c->k_act.p, c->k_r0.p, n, bits, c->q_temp.p, tb, c->q_key.p, c->q_idx0.p,
-                                   c->q_idx1.p, c->d_ns_active.p, c->k_tick.p, c->k_oflags.p, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out_count, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out_ok, c->k_oflags.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return OWGS_OK;
-}
-
-// ------------------------------------------------------------------------------------------ entitlement throttle gate
-// checkUserThrottle + checkConcurrentUserThrottle (Entitlement.scala:197-202, 354-381) for a drained batch; the
-// semantics are in include/owgs.h, the kernel in owgs_inflight.hip.
-int owgs_set_throttle_limits(owgs_ctx* c, int32_t invokes_per_minute, int32_t fires_per_minute,
-                             int32_t concurrent_invocations) {
-    if (!c) return OWGS_EINVAL;
-    c->lim_invoke = invokes_per_minute;
-    c->lim_fire = fires_per_minute;
-    c->lim_conc = concurrent_invocations;
-    return OWGS_OK;
-}
-
-// The gate's arguments that come from the context: the system defaults, the cluster size, the books and the rate
-// records.  The caller adds the batch's inputs (kind, t_ms, overrides) and where the five outputs go; shared by
-// owgs_admit_batch and owgs_invoke_activations.
-static OwgsAdmitArgs admit_args(const owgs_ctx* c, int32_t n) {
-    OwgsAdmitArgs A{};
-    A.n = n;
-    A.def_invoke = c->lim_invoke;
-    A.def_fire = c->lim_fire;
-    A.def_conc = c->lim_conc;
-    A.cluster = c->cluster;  // loadBalancer.clusterSize (SCPB:254)
-    A.active = c->d_ns_active.p;
-    A.rate_min = c->d_rate_min.p;
-    A.rate_cnt = c->d_rate_cnt.p;
-    A.ns_cap = c->ns_cap;
-    return A;
-}
-
-int owgs_admit_batch(owgs_ctx* c, int32_t n, const int32_t* ns, const uint8_t* kind, const int64_t* t_ms,
-                     const int32_t* rate_override, const int32_t* conc_override, uint8_t* out_verdict,
-                     int32_t* out_rate_count, int32_t* out_rate_limit, int32_t* out_conc_count,
-                     int32_t* out_conc_limit) {
-    if (!c || n < 0 ||
-        (n > 0 && (!ns || !kind || !t_ms || !out_verdict || !out_rate_count || !out_rate_limit || !out_conc_count ||
-                   !out_conc_limit)))
-        return OWGS_EINVAL;
-    if (n == 0) return OWGS_OK;
-    // argument contract: validated before any state changes
-    for (int32_t i = 0; i < n; ++i) {
-        if (ns[i] == OWGS_NONE) return c->fail(OWGS_EINVAL, "throttle gate without a namespace");
-        if (kind[i] & ~(OWGS_ADMIT_TRIGGER | OWGS_ADMIT_RATE_OVERRIDE | OWGS_ADMIT_CONC_OVERRIDE))
-            return c->fail(OWGS_EINVAL, "throttle gate: reserved kind bits");
-        if (((kind[i] & OWGS_ADMIT_RATE_OVERRIDE) && !rate_override) ||
-            ((kind[i] & OWGS_ADMIT_CONC_OVERRIDE) && !conc_override))
-            return c->fail(OWGS_EINVAL, "throttle gate: an override bit without its array");
-        if (t_ms[i] < 0 || t_ms[i] >= (1LL << 60)) return c->fail(OWGS_EINVAL, "throttle gate: time outside [0, 2^60)");
-    }
-    if (!ns_known(c, n, ns)) return c->fail(OWGS_ENOENT, "unknown namespace");
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    int32_t bits = 1;
-    while (((int64_t)1 << bits) < (int64_t)c->ns_map.size()) ++bits;
-    const size_t tb = owgs_throttle_sort_bytes(n, bits);
-    const size_t N = (size_t)n;
-    HIPCHK(c, c->q_temp.reserve(tb));
-    HIPCHK(c, c->q_key.reserve(N));
-    HIPCHK(c, c->q_idx0.reserve(N));
-    HIPCHK(c, c->q_idx1.reserve(N));
-    HIPCHK(c, upload(c->k_act, ns, N, c->stream));
-    HIPCHK(c, upload(c->k_kind, kind, N, c->stream));
-    HIPCHK(c, upload(c->k_off, t_ms, N, c->stream));
-    if (rate_override) HIPCHK(c, upload(c->k_r0, rate_override, N, c->stream));
-    if (conc_override) HIPCHK(c, upload(c->k_r1, conc_override, N, c->stream));
-    const size_t out_bytes = 17 * N;
-    HIPCHK(c, c->g_out.reserve(4 * N + (N + 3) / 4));
-    if (c->g_pin_bytes < out_bytes) {
-        if (c->g_pin) (void)hipHostFree(c->g_pin);
-        c->g_pin = nullptr;
-        c->g_pin_bytes = 0;
-        HIPCHK(c, hipHostMalloc(&c->g_pin, out_bytes * 2, hipHostMallocDefault));
-        c->g_pin_bytes = out_bytes * 2;
-    }
-    OwgsAdmitArgs A = admit_args(c, n);
-    A.kind = c->k_kind.p;
-    A.t_ms = c->k_off.p;
-    A.rate_ov = rate_override ? c->k_r0.p : nullptr;
-    A.conc_ov = conc_override ? c->k_r1.p : nullptr;
-    A.out_verdict = (uint8_t*)(c->g_out.p + 4 * N);
-    A.out_rate_count = c->g_out.p;
-    A.out_rate_limit = c->g_out.p + N;
-    A.out_conc_count = c->g_out.p + 2 * N;
-    A.out_conc_limit = c->g_out.p + 3 * N;
-    HIPCHK(c, owgs_launch_admit(c->k_act.p, bits, c->q_temp.p, tb, c->q_key.p, c->q_idx0.p, c->q_idx1.p, &A,
-                                c->stream));
-    // the five outputs come back with one copy into pinned memory (five copies into the caller's pageable arrays
-    // cost the call 55-71 us more) and are handed out on the host
-    HIPCHK(c, hipMemcpyAsync(c->g_pin, c->g_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const char* HO = (const char*)c->g_pin;
-    memcpy(out_rate_count, HO, 4 * N);
-    memcpy(out_rate_limit, HO + 4 * N, 4 * N);
-    memcpy(out_conc_count, HO + 8 * N, 4 * N);
-    memcpy(out_conc_limit, HO + 12 * N, 4 * N);
-    memcpy(out_verdict, HO + 16 * N, N);
-    return OWGS_OK;
-}
-
-int owgs_rate_state(owgs_ctx* c, int32_t n, const int32_t* ns, int32_t which, int64_t* out_last_min,
-                    int32_t* out_count) {
-    if (!c || n < 0 || which < 0 || which > 1 || (n > 0 && (!ns || !out_last_min || !out_count))) return OWGS_EINVAL;
-    if (n == 0) return OWGS_OK;
-    if (!ns_known(c, n, ns)) return c->fail(OWGS_ENOENT, "unknown namespace");
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    HIPCHK(c, upload(c->k_act, ns, (size_t)n, c->stream));
-    HIPCHK(c, c->g_min.reserve((size_t)n));
-    HIPCHK(c, c->k_tick.reserve((size_t)n));
-    HIPCHK(c, owgs_launch_rate_gather(c->d_rate_min.p, c->d_rate_cnt.p, c->ns_cap, which, c->k_act.p, n, c->g_min.p,
-                                      c->k_tick.p, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out_last_min, c->g_min.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out_count, c->k_tick.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return OWGS_OK;
-}
-
 // ------------------------------------------------------------------------------------------ health supervision
 // grow a persistent per-invoker array to cap entries, keeping the first `keep`
 template <class T>
@@ -4490,20 +2959,10 @@ static hipError_t grow_keep(DevBuf<T>& d, size_t cap, size_t keep, hipStream_t s
     if (e != hipSuccess) return e;
     if (keep && d.p) {
         e = hipMemcpyAsync(nb.p, d.p, keep * sizeof(T), hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) {
-            nb.release();
-            return e;
-        }
-        e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            nb.release();
-            return e;
-        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return e;
     }
-    d.release();
-    d = nb;
-    nb.p = nullptr;
-    nb.n = 0;
+    d = std::move(nb);
     return hipSuccess;
 }
 
@@ -4793,13 +3252,7 @@ int owgs_process_result_acks(owgs_ctx* c, int32_t n, const char* bytes, const in
         if (ro_) return ro_;
     }
     const size_t m = (size_t)n, blk_bytes = m * 38;
-    if (c->r_pin_bytes < blk_bytes) {
-        if (c->r_pin) (void)hipHostFree(c->r_pin);
-        c->r_pin = nullptr;
-        c->r_pin_bytes = 0;
-        HIPCHK(c, hipHostMalloc(&c->r_pin, blk_bytes * 2, hipHostMallocDefault));
-        c->r_pin_bytes = blk_bytes * 2;
-    }
+    if (c->r_pin.bytes < blk_bytes) HIPCHK(c, c->r_pin.reserve(blk_bytes * 2, hipHostMallocDefault));
     HIPCHK(c, c->r_blk.reserve(blk_bytes));
     unsigned long long* b_aid = (unsigned long long*)c->r_blk.p;
     int64_t* b_roff = (int64_t*)(b_aid + 2 * m);
@@ -4832,10 +3285,10 @@ int owgs_process_result_acks(owgs_ctx* c, int32_t n, const char* bytes, const in
     p.resp_len = b_rlen;
     HIPCHK(c, owgs_launch_ack_parse_results(&p, st));
     HIPCHK(c, hipMemcpyAsync(c->k_inst.p, b_inv, m * 4, hipMemcpyDeviceToDevice, st));
-    AckResultTail rt{b_aid, c->r_pin, c->r_blk.p, blk_bytes};
+    AckResultTail rt{b_aid, c->r_pin.p, c->r_blk.p, blk_bytes};
     int rc = ack_complete(c, n, b_kind, b_tick, b_flags, st, &rt);
     if (rc) return rc;
-    const char* P = (const char*)c->r_pin;
+    const char* P = (const char*)c->r_pin.p;
     memcpy(out->aid, P, m * 16);
     memcpy(out->resp_off, P + m * 16, m * 8);
     memcpy(out->invoker, P + m * 24, m * 4);
@@ -4920,686 +3373,6 @@ int owgs_process_pings(owgs_ctx* c, int32_t n, const char* bytes, const int64_t*
                         out_summary);
 }
 
-// ------------------------------------------------------------------------------------------ ActivationMessage output
-int owgs_register_templates(owgs_ctx* c, int32_t n, const char* a_bytes, const int64_t* a_off, const char* b_bytes,
-                            const int64_t* b_off, int32_t* out_first_id) {
-    if (!c || n < 0 || (n > 0 && (!a_bytes || !a_off || !b_bytes || !b_off))) return OWGS_EINVAL;
-    for (int32_t i = 0; i < n; ++i)
-        if (a_off[i + 1] < a_off[i] || b_off[i + 1] < b_off[i] || a_off[0] < 0 || b_off[0] < 0)
-            return c->fail(OWGS_EINVAL, "template offsets must be non-decreasing");
-    if ((int64_t)c->ta_off.size() - 1 + n > INT32_MAX) return c->fail(OWGS_ERANGE, "too many templates");
-    if (out_first_id) *out_first_id = (int32_t)c->ta_off.size() - 1;
-    for (int32_t i = 0; i < n; ++i) {
-        c->ta.insert(c->ta.end(), a_bytes + a_off[i], a_bytes + a_off[i + 1]);
-        c->ta_off.push_back((int64_t)c->ta.size());
-        c->tb.insert(c->tb.end(), b_bytes + b_off[i], b_bytes + b_off[i + 1]);
-        c->tb_off.push_back((int64_t)c->tb.size());
-    }
-    c->tmpl_dirty = true;
-    return OWGS_OK;
-}
-
-int owgs_set_root_controller(owgs_ctx* c, const char* json, int32_t len) {
-    if (!c || len < 0 || (len > 0 && !json)) return OWGS_EINVAL;
-    c->rci.assign(json, json + len);
-    c->tmpl_dirty = true;
-    return OWGS_OK;
-}
-
-static int msg_templates_upload(owgs_ctx* c, hipStream_t st) {
-    if (!c->tmpl_dirty) return OWGS_OK;
-    HIPCHK(c, upload(c->m_ta, c->ta.data(), c->ta.size(), st));
-    HIPCHK(c, upload(c->m_tb, c->tb.data(), c->tb.size(), st));
-    HIPCHK(c, upload(c->m_ta_off, c->ta_off.data(), c->ta_off.size(), st));
-    HIPCHK(c, upload(c->m_tb_off, c->tb_off.data(), c->tb_off.size(), st));
-    HIPCHK(c, upload(c->m_rci, c->rci.data(), c->rci.size(), st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    c->tmpl_dirty = false;
-    return OWGS_OK;
-}
-
-// plan + write with device pointers, queued on st without a wait.  The templates are on the device already
-// (msg_templates_upload, which may wait).
-static int msg_queue(owgs_ctx* c, OwgsMsgArgs& A, int32_t n_topics, hipStream_t st) {
-    const int32_t n = A.n;
-    A.ta = c->m_ta.p;
-    A.ta_off = c->m_ta_off.p;
-    A.tb = c->m_tb.p;
-    A.tb_off = c->m_tb_off.p;
-    A.n_templates = (int32_t)c->ta_off.size() - 1;
-    A.rci = c->m_rci.p;
-    A.rci_len = (int32_t)c->rci.size();
-    A.n_topics = n_topics;
-    int32_t bits = 1;
-    while (bits < 31 && ((int64_t)n_topics >> bits) != 0) ++bits;
-    HIPCHK(c, c->m_key.reserve((size_t)n));
-    HIPCHK(c, c->m_key_sorted.reserve((size_t)n));
-    HIPCHK(c, c->m_len.reserve((size_t)n));
-    HIPCHK(c, c->m_len_sorted.reserve((size_t)n + 1));
-    HIPCHK(c, c->m_iota.reserve((size_t)n));
-    HIPCHK(c, c->m_cnt.reserve((size_t)n_topics + 1));
-    HIPCHK(c, c->m_bad.reserve(1));
-    const size_t tb = owgs_msg_scratch_bytes(n, n_topics, bits);
-    HIPCHK(c, c->m_temp.reserve(tb));
-    A.key = c->m_key.p;
-    A.len = c->m_len.p;
-    A.bad = c->m_bad.p;
-    HIPCHK(c, hipMemsetAsync(c->m_bad.p, 0, 4, st));
-    HIPCHK(c, owgs_launch_msg_plan(&A, bits, c->m_temp.p, tb, c->m_key_sorted.p, c->m_iota.p, c->m_len_sorted.p,
-                                   c->m_cnt.p, st));
-    HIPCHK(c, owgs_launch_msg_write(&A, st));
-    return OWGS_OK;
-}
-
-// the message stage's verdict from its bad-input word
-static int msg_verdict(owgs_ctx* c, int32_t bad) {
-    if (bad & 1) return c->fail(OWGS_EINVAL, "serialize: invoker >= n_topics or unknown template");
-    if (bad & 2) return c->fail(OWGS_EINVAL, "serialize: transaction id is not valid UTF-8");
-    if (bad & 4) return c->fail(OWGS_ERANGE, "serialize: output capacity below the batch's bytes (see *total)");
-    return OWGS_OK;
-}
-
-// queue + finish: host-visible *total / *m (one wait)
-static int msg_run(owgs_ctx* c, OwgsMsgArgs& A, int32_t n_topics, hipStream_t st, int64_t* total, int32_t* m) {
-    int rc = msg_templates_upload(c, st);
-    if (!rc) rc = msg_queue(c, A, n_topics, st);
-    if (rc) return rc;
-    int32_t bad = 0, mm = 0;
-    int64_t tot = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, c->m_bad.p, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&mm, A.topic_start + n_topics, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&tot, A.out_off + A.n, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (total) *total = tot;
-    if (m) *m = mm;
-    return msg_verdict(c, bad);
-}
-
-// fused: the batch of owgs_publish_activations, whose invoker and aid are the call's own (both must be NULL)
-static bool msg_batch_ok(const owgs_msg_batch* b, int32_t n_topics, bool fused = false) {
-    if (!b || b->n < 0 || n_topics < 0 || n_topics >= INT32_MAX) return false;
-    if (fused && (b->invoker || b->aid)) return false;
-    if (b->n == 0) return true;
-    return (fused || (b->invoker && b->aid)) && b->tmpl && b->tid_off && b->tid_start && b->flags;
-}
-
-struct MsgNeeds {
-    bool c = false, r = false, x = false;  // some flag asks for content / traceContext / cause
-};
-
-// the host-side checks of a batch in host buffers and of its outputs, before anything is touched
-static int msg_host_check(owgs_ctx* c, const owgs_msg_batch* b, int32_t n_topics, const char* out, int64_t cap,
-                          const int64_t* out_off, const int32_t* out_order, const int32_t* topic_start, bool fused,
-                          MsgNeeds& need) {
-    if (!c || !msg_batch_ok(b, n_topics, fused) || cap < 0 || !out_off || !topic_start || (b->n > 0 && !out_order) ||
-        (cap > 0 && !out))
-        return OWGS_EINVAL;
-    const int32_t n = b->n;
-    if (n > 0 && b->tid_off[n] > b->tid_off[0] && !b->tid)
-        return c->fail(OWGS_EINVAL, "serialize: transaction id bytes missing");
-    for (int32_t i = 0; i < n; ++i) {
-        need.c |= (b->flags[i] & OWGS_MSG_HAS_CONTENT) != 0;
-        need.x |= (b->flags[i] & OWGS_MSG_HAS_CAUSE) != 0;
-        need.r |= (b->flags[i] & OWGS_MSG_HAS_TRACE) != 0;
-    }
-    if ((need.c && (!b->content || !b->content_off)) || (need.x && !b->cause) ||
-        (need.r && (!b->trace || !b->trace_off)))
-        return c->fail(OWGS_EINVAL, "serialize: a flag asks for content / cause / traceContext that is missing");
-    for (int32_t i = 0; i < n; ++i)
-        if (b->tid_off[i + 1] < b->tid_off[i] || (need.c && b->content_off[i + 1] < b->content_off[i]) ||
-            (need.r && b->trace_off[i + 1] < b->trace_off[i]))
-            return c->fail(OWGS_EINVAL, "serialize: offsets must be non-decreasing");
-    return OWGS_OK;
-}
-
-// a checked host batch -> the context's device buffers, outputs reserved; A is complete but for invoker and aid
-static int msg_upload(owgs_ctx* c, const owgs_msg_batch* b, const MsgNeeds& need, int32_t n_topics, int64_t cap,
-                      OwgsMsgArgs& A, hipStream_t st) {
-    const int32_t n = b->n;
-    const int64_t tid0 = n ? b->tid_off[0] : 0, tidn = n ? b->tid_off[n] : 0;
-    HIPCHK(c, upload(c->m_tmpl, b->tmpl, (size_t)n, st));
-    HIPCHK(c, upload(c->m_tid, b->tid + tid0, (size_t)(tidn - tid0), st));
-    std::vector<int64_t> off((size_t)n + 1);
-    for (int32_t i = 0; i <= n; ++i) off[i] = n ? b->tid_off[i] - tid0 : 0;
-    HIPCHK(c, upload(c->m_tid_off, off.data(), off.size(), st));
-    HIPCHK(c, upload(c->m_tid_start, b->tid_start, (size_t)n, st));
-    HIPCHK(c, upload(c->m_flags, b->flags, (size_t)n, st));
-    std::vector<int64_t> coff((size_t)n + 1, 0), roff((size_t)n + 1, 0);
-    if (need.c) {
-        for (int32_t i = 0; i <= n; ++i) coff[i] = b->content_off[i] - b->content_off[0];
-        HIPCHK(c, upload(c->m_content, b->content + b->content_off[0], (size_t)coff[n], st));
-    }
-    if (need.r) {
-        for (int32_t i = 0; i <= n; ++i) roff[i] = b->trace_off[i] - b->trace_off[0];
-        HIPCHK(c, upload(c->m_trace, b->trace + b->trace_off[0], (size_t)roff[n], st));
-    }
-    HIPCHK(c, upload(c->m_content_off, coff.data(), coff.size(), st));
-    HIPCHK(c, upload(c->m_trace_off, roff.data(), roff.size(), st));
-    if (need.x) HIPCHK(c, upload(c->m_cause, (const ulonglong2*)b->cause, (size_t)n, st));
-    else HIPCHK(c, c->m_cause.reserve(1));
-    HIPCHK(c, c->m_content.reserve(1));
-    HIPCHK(c, c->m_trace.reserve(1));
-    HIPCHK(c, c->m_order.reserve((size_t)n));
-    HIPCHK(c, c->m_out_off.reserve((size_t)n + 1));
-    HIPCHK(c, c->m_topic.reserve((size_t)n_topics + 1));
-    HIPCHK(c, c->m_out.reserve((size_t)std::max<int64_t>(cap, 1)));
-    A.n = n;
-    A.tmpl = c->m_tmpl.p;
-    A.tid = c->m_tid.p;
-    A.tid_off = c->m_tid_off.p;
-    A.tid_start = c->m_tid_start.p;
-    A.flags = c->m_flags.p;
-    A.content = c->m_content.p;
-    A.content_off = c->m_content_off.p;
-    A.cause = c->m_cause.p;
-    A.trace = c->m_trace.p;
-    A.trace_off = c->m_trace_off.p;
-    A.order = c->m_order.p;
-    A.out_off = c->m_out_off.p;
-    A.topic_start = c->m_topic.p;
-    A.out = c->m_out.p;
-    A.cap = cap;
-    return OWGS_OK;
-}
-
-// the serialised batch (tot bytes, mm messages) from the context's device buffers into the caller's; waits
-static int msg_download(owgs_ctx* c, int32_t n_topics, int64_t tot, int32_t mm, char* out, int64_t* out_off,
-                        int32_t* out_order, int32_t* topic_start, hipStream_t st) {
-    if (tot) HIPCHK(c, hipMemcpyAsync(out, c->m_out.p, (size_t)tot, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(out_off, c->m_out_off.p, (size_t)(mm + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (mm) HIPCHK(c, hipMemcpyAsync(out_order, c->m_order.p, (size_t)mm * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(topic_start, c->m_topic.p, (size_t)(n_topics + 1) * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    return OWGS_OK;
-}
-
-int owgs_serialize_activations(owgs_ctx* c, const owgs_msg_batch* b, int32_t n_topics, char* out, int64_t cap,
-                               int64_t* out_off, int32_t* out_order, int32_t* topic_start, int64_t* total,
-                               int32_t* m) {
-    MsgNeeds need;
-    int rc = msg_host_check(c, b, n_topics, out, cap, out_off, out_order, topic_start, false, need);
-    if (rc) return rc;
-    const int32_t n = b->n;
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    hipStream_t st = c->stream;
-    HIPCHK(c, upload(c->m_inv, b->invoker, (size_t)n, st));
-    HIPCHK(c, upload(c->m_aid, (const ulonglong2*)b->aid, (size_t)n, st));
-    OwgsMsgArgs A{};
-    rc = msg_upload(c, b, need, n_topics, cap, A, st);
-    if (rc) return rc;
-    A.invoker = c->m_inv.p;
-    A.aid = c->m_aid.p;
-    int64_t tot = 0;
-    int32_t mm = 0;
-    rc = msg_run(c, A, n_topics, st, &tot, &mm);
-    if (total) *total = tot;
-    if (m) *m = mm;
-    if (rc) return rc;
-    return msg_download(c, n_topics, tot, mm, out, out_off, out_order, topic_start, st);
-}
-
-int owgs_serialize_activations_device(owgs_ctx* c, const owgs_msg_batch* b, int32_t n_topics, char* out,
-                                      int64_t cap, int64_t* out_off, int32_t* out_order, int32_t* topic_start,
-                                      int64_t* total, int32_t* m, void* stream) {
-    if (!c || !msg_batch_ok(b, n_topics) || cap < 0 || !out_off || !topic_start || (b->n > 0 && !out_order) ||
-        (cap > 0 && !out) || (b->n > 0 && (!b->content_off || !b->trace_off)))
-        return OWGS_EINVAL;
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, stream ? (hipStream_t)stream : c->stream);
-        if (ro_) return ro_;
-    }
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, c->m_content.reserve(1));
-    HIPCHK(c, c->m_trace.reserve(1));
-    HIPCHK(c, c->m_cause.reserve(1));
-    OwgsMsgArgs A{};
-    A.n = b->n;
-    A.invoker = b->invoker;
-    A.tmpl = b->tmpl;
-    A.aid = (const ulonglong2*)b->aid;
-    A.tid = b->tid;
-    A.tid_off = b->tid_off;
-    A.tid_start = b->tid_start;
-    A.flags = b->flags;
-    A.content = b->content ? b->content : c->m_content.p;
-    A.content_off = b->content_off;
-    A.cause = b->cause ? (const ulonglong2*)b->cause : c->m_cause.p;
-    A.trace = b->trace ? b->trace : c->m_trace.p;
-    A.trace_off = b->trace_off;
-    A.order = out_order;
-    A.out_off = out_off;
-    A.topic_start = topic_start;
-    A.out = out;
-    A.cap = cap;
-    return msg_run(c, A, n_topics, st, total, m);
-}
-
-// ------------------------------------------------------------------------------------------ publish end to end
-// Where the four publish arrays of an output block lie in pinned memory (the header is at c->p_pin).
-struct PublishBlock {
-    const char *inv, *ticket, *flags, *existed;
-};
-
-// What owgs_publish_activations and owgs_invoke_activations do once their output block has arrived in c->p_pin: the
-// engine's error word as the gate kernel saw it, the four publish outputs handed out, the host's share of the books
-// (the table's fill, CLB:121-125 for every placed item), out_summary[0..6], the table-full scan and, with msgs, the
-// message stage's verdict and the download of its bytes.  who names the entry point in the error texts.
-static int publish_tail(owgs_ctx* c, const char* who, int32_t n, const PublishBlock& B, int32_t* out_invoker,
-                        uint8_t* out_flags, int32_t* out_ticket, uint8_t* out_existed, const owgs_msg_batch* msgs,
-                        owgs_msg_out* mo, int64_t* out_summary, hipStream_t st) {
-    const unsigned long long* H = (const unsigned long long*)c->p_pin;
-    if (H[OWGS_PUB_ERR]) {  // the engine failed: the gate placed nothing, the table and the books are untouched
-        const int rc = check_err_word(c);
-        return rc ? rc : c->fail(OWGS_EDEVICE, (std::string(who) + ": the engine's error word was set").c_str());
-    }
-    memcpy(out_invoker, B.inv, (size_t)n * 4);
-    memcpy(out_ticket, B.ticket, (size_t)n * 4);
-    memcpy(out_flags, B.flags, (size_t)n);
-    memcpy(out_existed, B.existed, (size_t)n);
-    const long long placed = (long long)H[OWGS_PUB_PLACED], inserted = (long long)H[OWGS_PUB_CNT + OWGS_CNT_INSERTED];
-    c->t_used += inserted;
-    c->t_live += inserted;
-    // CLB:121-125 for every placed item, duplicates included; an item without an invoker never reaches them
-    c->f_total += placed;
-    c->f_mb_managed += (long long)H[OWGS_PUB_CNT + OWGS_CNT_MANAGED_MB];
-    c->f_mb_blackbox += (long long)H[OWGS_PUB_CNT + OWGS_CNT_BLACKBOX_MB];
-    out_summary[0] = placed;
-    out_summary[1] = inserted;
-    out_summary[2] = (int64_t)H[OWGS_PUB_OVL_MANAGED];
-    out_summary[3] = (int64_t)H[OWGS_PUB_OVL_BLACKBOX];
-    out_summary[4] = (int64_t)H[OWGS_PUB_NONE];
-    out_summary[5] = (int64_t)H[OWGS_PUB_THROW];
-    out_summary[6] = 2;
-    for (int32_t i = 0; i < n; ++i)
-        if (out_existed[i] == 2) return c->fail(OWGS_EDEVICE, (std::string(who) + ": activation table full").c_str());
-    if (!msgs) return OWGS_OK;
-    const int32_t mm = (int32_t)H[OWGS_PUB_MSG_M];
-    const int64_t tot = (int64_t)H[OWGS_PUB_MSG_TOTAL];
-    mo->total = tot;
-    mo->m = mm;
-    int rc = msg_verdict(c, (int32_t)H[OWGS_PUB_MSG_BAD]);
-    if (!rc) rc = msg_download(c, mo->n_topics, tot, mm, mo->out, mo->out_off, mo->out_order, mo->topic_start, st);
-    if (rc) return rc;  // the entries stay, left to their timeouts (SCPB:302-303): serialise again with out_invoker
-    out_summary[6] = 3;
-    return OWGS_OK;
-}
-
-// ShardingContainerPoolBalancer.publish (SCPB:257-317) for a drained batch: schedule, setupActivation for the placed
-// items, the serialised messages -- the decisions never leave the device between the stages.  On an
-// on-chip context nothing below waits between queueing the engine and the one block copy; the gate kernel reads the
-// error word on the device, so an engine error leaves the later stages with nothing to do.
-int owgs_publish_activations(owgs_ctx* c, const owgs_publish_io* io, const owgs_msg_batch* msgs, owgs_msg_out* mo,
-                             int64_t out_summary[8]) {
-    if (!c || !io || !out_summary) return OWGS_EINVAL;
-    const int32_t n = io->n;
-    if (n < 0 || (msgs == nullptr) != (mo == nullptr)) return OWGS_EINVAL;
-    if (n > 0 && (!io->action || !io->aid || !io->ticket || !io->time_limit_ms || !io->out_invoker ||
-                  !io->out_flags || !io->out_ticket || !io->out_existed))
-        return OWGS_EINVAL;
-    MsgNeeds need;
-    if (msgs) {
-        if (msgs->n != n) return c->fail(OWGS_EINVAL, "publish: msgs->n differs from io->n");
-        const int rm = msg_host_check(c, msgs, mo->n_topics, mo->out, mo->cap, mo->out_off, mo->out_order,
-                                      mo->topic_start, true, need);
-        if (rm) return rm;
-    }
-    if (io->now_ms < 0 || io->now_ms >= (1LL << 60)) return c->fail(OWGS_EINVAL, "publish: now outside [0, 2^60)");
-    for (int32_t i = 0; i < n; ++i)
-        if (io->time_limit_ms[i] < 0 || io->time_limit_ms[i] >= (1LL << 40))
-            return c->fail(OWGS_EINVAL, "publish: time limit outside [0, 2^40)");
-    if (!registered(c, n, io->action)) return c->fail(OWGS_ENOENT, "unknown action");
-    if (io->ns) {
-        const int32_t nn = (int32_t)c->ns_map.size();
-        for (int32_t i = 0; i < n; ++i)
-            if (io->ns[i] != OWGS_NONE && (io->ns[i] < 0 || io->ns[i] >= nn))
-                return c->fail(OWGS_ENOENT, "unknown namespace");
-    }
-    for (int k = 0; k < 8; ++k) out_summary[k] = 0;
-    if (n == 0) {
-        if (mo) {
-            mo->total = 0;
-            mo->m = 0;
-            mo->out_off[0] = 0;
-            for (int32_t k = 0; k <= mo->n_topics; ++k) mo->topic_start[k] = 0;
-            out_summary[6] = 3;
-        } else {
-            out_summary[6] = 2;
-        }
-        return OWGS_OK;
-    }
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    hipStream_t st = c->stream;
-    // everything that may wait comes first: the table's rehash, the templates, the buffers
-    int rc = act_reserve(c, n);
-    if (!rc && msgs) rc = msg_templates_upload(c, st);
-    if (rc) return rc;
-    const size_t hdr_bytes = (size_t)OWGS_PUB_HDR * 8, blk_bytes = hdr_bytes + (size_t)n * 10;
-    if (c->p_pin_bytes < blk_bytes) {
-        if (c->p_pin) (void)hipHostFree(c->p_pin);
-        c->p_pin = nullptr;
-        c->p_pin_bytes = 0;
-        HIPCHK(c, hipHostMalloc(&c->p_pin, blk_bytes * 2, hipHostMallocDefault));
-        c->p_pin_bytes = blk_bytes * 2;
-    }
-    HIPCHK(c, c->p_blk.reserve(blk_bytes));
-    HIPCHK(c, c->p_placed.reserve((size_t)n));
-    if (msgs) HIPCHK(c, c->p_minv.reserve((size_t)n));
-    // stage 1: the decisions, left in d_out / d_flags (the action handles in d_a)
-    rc = publish_device(c, n, io->action, io->seq, io->seq_base, nullptr, nullptr);
-    if (rc) return rc;  // (only the large-state engine reports its own error here: nothing is tracked or written)
-    // the inputs of stages 2 and 3 go up while the engine runs
-    HIPCHK(c, upload(c->k_key, (const ulonglong2*)io->aid, (size_t)n, st));
-    HIPCHK(c, upload(c->k_r0, io->ticket, (size_t)n, st));
-    if (io->ns) HIPCHK(c, upload(c->k_r1, io->ns, (size_t)n, st));
-    HIPCHK(c, upload(c->x_tl, (const long long*)io->time_limit_ms, (size_t)n, st));
-    OwgsMsgArgs A{};
-    if (msgs) {
-        rc = msg_upload(c, msgs, need, mo->n_topics, mo->cap, A, st);
-        if (rc) return rc;
-    }
-    unsigned long long* hdr = (unsigned long long*)c->p_blk.p;
-    int32_t* b_inv = (int32_t*)(c->p_blk.p + hdr_bytes);
-    int32_t* b_tick = b_inv + n;
-    uint8_t* b_flags = (uint8_t*)(b_tick + n);
-    uint8_t* b_ex = b_flags + n;
-    HIPCHK(c, hipMemsetAsync(hdr, 0, hdr_bytes, st));
-    OwgsPublishGate G{};
-    G.n = n;
-    G.err = c->d_err.p;
-    G.dec = c->d_out.p;
-    G.dflags = c->d_flags.p;
-    G.action = c->d_a.p;
-    G.act_bb = c->d_act_bb.p;
-    G.placed = c->p_placed.p;
-    G.msg_inv = msgs ? c->p_minv.p : nullptr;
-    G.hdr = hdr;
-    G.out_inv = b_inv;
-    G.out_ticket = b_tick;
-    G.out_flags = b_flags;
-    G.out_existed = b_ex;
-    HIPCHK(c, owgs_launch_publish_gate(&G, st));
-    // stage 2: setupActivation of the placed items, the entry's invoker read from the decisions
-    rc = track_device(c, n, c->k_key.p, c->d_a.p, io->ns ? c->k_r1.p : nullptr, c->k_r0.p, c->d_out.p, c->x_tl.p,
-                      io->now_ms, c->p_placed.p, b_tick, b_ex, hdr + OWGS_PUB_CNT, st);
-    if (rc) return rc;
-    // stage 3: the messages of the placed items
-    if (msgs) {
-        A.invoker = c->p_minv.p;
-        A.aid = c->k_key.p;
-        rc = msg_queue(c, A, mo->n_topics, st);
-        if (rc) return rc;
-        HIPCHK(c, owgs_launch_publish_collect(hdr, c->m_bad.p, A.topic_start, mo->n_topics, A.out_off, n, st));
-    }
-    HIPCHK(c, hipMemcpyAsync(c->p_pin, c->p_blk.p, blk_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    const char* P = (const char*)c->p_pin + hdr_bytes;
-    const PublishBlock B{P, P + (size_t)n * 4, P + (size_t)n * 8, P + (size_t)n * 9};
-    return publish_tail(c, "publish", n, B, io->out_invoker, io->out_flags, io->out_ticket, io->out_existed, msgs, mo,
-                        out_summary, st);
-}
-
-// ------------------------------------------------------------------------------------------ gated publish
-// The engine step of owgs_invoke_activations on an on-chip context: publish_device without its uploads.  The admitted
-// actions are in d_a (and d_seq) and their count m only on the device, as the batch offsets {0, m} in d_off; n bounds
-// it.  Checked against m on the device: the pre-pass and the engine take every bound from d_off, the
-// host count sizes buffers (d_rec, d_lix, the pre-pass grid, the overflow's upper bound) and clamps the I/O wave's
-// record prefetch; the watch update runs over n items, of which those from m on are padding it returns on.
-static int invoke_engine(owgs_ctx* c, int32_t n, bool has_seq, uint64_t seq_base) {
-    OwgsEngineArgs A;
-    base_args(c, A);
-    A.seq_base = seq_base;
-    A.seq = has_seq ? c->d_seq.p : nullptr;
-    A.out_inv = c->d_out.p;
-    A.out_flags = c->d_flags.p;
-    int rc = run_prepass(c, A, 1, c->d_off.p, c->d_a.p, n, c->stream);
-    if (!rc) rc = run_engine(c, A, c->stream);
-    if (!rc) rc = w_update(c, n, c->d_a.p, c->d_out.p, c->d_flags.p, c->stream);
-    return rc;
-}
-
-// EntitlementProvider.checkThrottles (Entitlement.scala:197-202, 354-381) and, for what it admits,
-// ShardingContainerPoolBalancer.publish (SCPB:257-317) for a drained batch (the semantics are in
-// include/owgs.h).  On an on-chip context nothing below waits between queueing the gate and the one block copy.
-int owgs_invoke_activations(owgs_ctx* c, const owgs_invoke_io* io, const owgs_msg_batch* msgs, owgs_msg_out* mo,
-                            int64_t out_summary[16]) {
-    if (!c || !io || !out_summary) return OWGS_EINVAL;
-    const int32_t n = io->n;
-    if (n < 0 || (msgs == nullptr) != (mo == nullptr)) return OWGS_EINVAL;
-    if (n > 0 && (!io->ns || !io->kind || !io->t_ms || !io->action || !io->aid || !io->ticket || !io->time_limit_ms ||
-                  !io->out_verdict || !io->out_rate_count || !io->out_rate_limit || !io->out_conc_count ||
-                  !io->out_conc_limit || !io->out_invoker || !io->out_flags || !io->out_ticket || !io->out_existed))
-        return OWGS_EINVAL;
-    // the gate's argument contract (owgs_admit_batch)
-    for (int32_t i = 0; i < n; ++i) {
-        const uint8_t kd = io->kind[i];
-        if (io->ns[i] == OWGS_NONE) return c->fail(OWGS_EINVAL, "throttle gate without a namespace");
-        if (kd & ~(OWGS_ADMIT_TRIGGER | OWGS_ADMIT_RATE_OVERRIDE | OWGS_ADMIT_CONC_OVERRIDE))
-            return c->fail(OWGS_EINVAL, "throttle gate: reserved kind bits");
-        if (((kd & OWGS_ADMIT_RATE_OVERRIDE) && !io->rate_override) ||
-            ((kd & OWGS_ADMIT_CONC_OVERRIDE) && !io->conc_override))
-            return c->fail(OWGS_EINVAL, "throttle gate: an override bit without its array");
-        if (io->t_ms[i] < 0 || io->t_ms[i] >= (1LL << 60))
-            return c->fail(OWGS_EINVAL, "throttle gate: time outside [0, 2^60)");
-    }
-    // ... and publish's (owgs_publish_activations), over the items that are actions
-    MsgNeeds need;
-    if (msgs) {
-        if (msgs->n != n) return c->fail(OWGS_EINVAL, "invoke: msgs->n differs from io->n");
-        const int rm = msg_host_check(c, msgs, mo->n_topics, mo->out, mo->cap, mo->out_off, mo->out_order,
-                                      mo->topic_start, true, need);
-        if (rm) return rm;
-    }
-    if (io->now_ms < 0 || io->now_ms >= (1LL << 60)) return c->fail(OWGS_EINVAL, "invoke: now outside [0, 2^60)");
-    for (int32_t i = 0; i < n; ++i)
-        if (!(io->kind[i] & OWGS_ADMIT_TRIGGER) && (io->time_limit_ms[i] < 0 || io->time_limit_ms[i] >= (1LL << 40)))
-            return c->fail(OWGS_EINVAL, "invoke: time limit outside [0, 2^40)");
-    for (int32_t i = 0; i < n; ++i)
-        if (!(io->kind[i] & OWGS_ADMIT_TRIGGER) && !registered(c, 1, io->action + i))
-            return c->fail(OWGS_ENOENT, "unknown action");
-    if (!ns_known(c, n, io->ns)) return c->fail(OWGS_ENOENT, "unknown namespace");
-    for (int k = 0; k < 16; ++k) out_summary[k] = 0;
-    if (n == 0) {
-        if (mo) {
-            mo->total = 0;
-            mo->m = 0;
-            mo->out_off[0] = 0;
-            for (int32_t k = 0; k <= mo->n_topics; ++k) mo->topic_start[k] = 0;
-            out_summary[6] = 3;
-        } else {
-            out_summary[6] = 2;
-        }
-        return OWGS_OK;
-    }
-    OWGS_ENTER(c);
-    {
-        const int ro_ = order_on(c, c->stream);
-        if (ro_) return ro_;
-    }
-    hipStream_t st = c->stream;
-    const size_t N = (size_t)n;
-    // everything that may wait comes first: the table's rehash, the templates, the buffers
-    int rc = act_reserve(c, n);
-    if (!rc && msgs) rc = msg_templates_upload(c, st);
-    if (rc) return rc;
-    const size_t hdr_bytes = (size_t)OWGS_PUB_HDR * 8, blk_bytes = hdr_bytes + N * 27;
-    if (c->p_pin_bytes < blk_bytes) {
-        if (c->p_pin) (void)hipHostFree(c->p_pin);
-        c->p_pin = nullptr;
-        c->p_pin_bytes = 0;
-        HIPCHK(c, hipHostMalloc(&c->p_pin, blk_bytes * 2, hipHostMallocDefault));
-        c->p_pin_bytes = blk_bytes * 2;
-    }
-    HIPCHK(c, c->p_blk.reserve(blk_bytes));
-    HIPCHK(c, c->p_placed.reserve(N));
-    if (msgs) HIPCHK(c, c->p_minv.reserve(N));
-    int32_t bits = 1;
-    while (((int64_t)1 << bits) < (int64_t)c->ns_map.size()) ++bits;
-    const size_t tb = owgs_throttle_sort_bytes(n, bits);
-    HIPCHK(c, c->q_temp.reserve(tb));
-    HIPCHK(c, c->q_key.reserve(N));
-    HIPCHK(c, c->q_idx0.reserve(N));
-    HIPCHK(c, c->q_idx1.reserve(N));
-    HIPCHK(c, c->v_rank.reserve(N));
-    HIPCHK(c, c->d_out.reserve(N));
-    HIPCHK(c, c->d_flags.reserve(N));
-    // the block: header, then the gate's four int32 arrays, out_invoker, out_ticket, then the three byte arrays
-    unsigned long long* hdr = (unsigned long long*)c->p_blk.p;
-    int32_t* b_rc = (int32_t*)(c->p_blk.p + hdr_bytes);
-    int32_t *b_rl = b_rc + N, *b_cc = b_rc + 2 * N, *b_cl = b_rc + 3 * N, *b_inv = b_rc + 4 * N, *b_tick = b_rc + 5 * N;
-    uint8_t *b_ver = (uint8_t*)(b_rc + 6 * N), *b_flags = b_ver + N, *b_ex = b_ver + 2 * N;
-    HIPCHK(c, hipMemsetAsync(hdr, 0, hdr_bytes, st));
-    // stage 0: the gate (owgs_admit_batch), its outputs written into the block
-    HIPCHK(c, upload(c->k_act, io->ns, N, st));
-    HIPCHK(c, upload(c->k_kind, io->kind, N, st));
-    HIPCHK(c, upload(c->k_off, io->t_ms, N, st));
-    if (io->rate_override) HIPCHK(c, upload(c->v_ov0, io->rate_override, N, st));
-    if (io->conc_override) HIPCHK(c, upload(c->v_ov1, io->conc_override, N, st));
-    OwgsAdmitArgs G = admit_args(c, n);
-    G.kind = c->k_kind.p;
-    G.t_ms = c->k_off.p;
-    G.rate_ov = io->rate_override ? c->v_ov0.p : nullptr;
-    G.conc_ov = io->conc_override ? c->v_ov1.p : nullptr;
-    G.out_verdict = b_ver;
-    G.out_rate_count = b_rc;
-    G.out_rate_limit = b_rl;
-    G.out_conc_count = b_cc;
-    G.out_conc_limit = b_cl;
-    HIPCHK(c, owgs_launch_admit(c->k_act.p, bits, c->q_temp.p, tb, c->q_key.p, c->q_idx0.p, c->q_idx1.p, &G, st));
-    int64_t waits = 0;
-    // the five gate outputs from the pinned block (valid whenever the gate ran, whatever happens after it)
-    auto gate_out = [&]() {
-        const char* P = (const char*)c->p_pin + hdr_bytes;
-        memcpy(io->out_rate_count, P, 4 * N);
-        memcpy(io->out_rate_limit, P + 4 * N, 4 * N);
-        memcpy(io->out_conc_count, P + 8 * N, 4 * N);
-        memcpy(io->out_conc_limit, P + 12 * N, 4 * N);
-        memcpy(io->out_verdict, P + 24 * N, N);
-        for (int32_t i = 0; i < n; ++i) {
-            const bool trig = (io->kind[i] & OWGS_ADMIT_TRIGGER) != 0;
-            const uint8_t v = io->out_verdict[i];
-            out_summary[8] += !trig && v == OWGS_ADMIT_OK;
-            out_summary[9] += v == OWGS_ADMIT_RATE;
-            out_summary[10] += v == OWGS_ADMIT_CONCURRENT;
-            out_summary[11] += trig && v == OWGS_ADMIT_OK;
-        }
-    };
-    // the engine step failed on the host side or reported its own error: the rate records stay charged and the gate's
-    // outputs are handed out (the reference charges the rate before publish can fail); nothing is tracked or written
-    auto engine_failed = [&](int code) {
-        if (hipMemcpyAsync(c->p_pin, c->p_blk.p, blk_bytes, hipMemcpyDeviceToHost, st) == hipSuccess &&
-            hipStreamSynchronize(st) == hipSuccess) {
-            gate_out();
-            out_summary[12] = waits + 1;
-        }
-        return code;
-    };
-    // stage 1: the admitted actions through the engine, the decisions left in d_out / d_flags by rank
-    if (c->large) {
-        // the large-state engine's run takes host arrays: the verdicts come back once before it
-        std::vector<uint8_t> ver(N);
-        HIPCHK(c, hipMemcpyAsync(ver.data(), b_ver, N, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        ++waits;
-        std::vector<int32_t> rank(N), act_c;
-        std::vector<uint64_t> seq_c;
-        for (int32_t i = 0; i < n; ++i) {
-            const bool adm = !(io->kind[i] & OWGS_ADMIT_TRIGGER) && ver[i] == OWGS_ADMIT_OK;
-            rank[i] = adm ? (int32_t)act_c.size() : -1;
-            if (adm) {
-                act_c.push_back(io->action[i]);
-                if (io->seq) seq_c.push_back(io->seq[i]);
-            }
-        }
-        HIPCHK(c, upload(c->v_rank, rank.data(), N, st));
-        if (!act_c.empty())
-            rc = publish_device(c, (int32_t)act_c.size(), act_c.data(), io->seq ? seq_c.data() : nullptr, io->seq_base,
-                                nullptr, nullptr);
-        if (rc) return engine_failed(rc);
-    } else {
-        HIPCHK(c, c->d_off.reserve(2));
-        HIPCHK(c, c->d_a.reserve(N));
-        if (io->seq) HIPCHK(c, c->d_seq.reserve(N));
-        HIPCHK(c, c->v_map.reserve(N));
-        HIPCHK(c, c->v_bcnt.reserve((N + 255) / 256));
-        HIPCHK(c, upload(c->v_act, io->action, N, st));
-        if (io->seq) HIPCHK(c, upload(c->v_seq, (const u64*)io->seq, N, st));
-        OwgsInvokeCompact K{};
-        K.n = n;
-        K.verdict = b_ver;
-        K.kind = c->k_kind.p;
-        K.action = c->v_act.p;
-        K.seq = io->seq ? c->v_seq.p : nullptr;
-        K.bcnt = c->v_bcnt.p;
-        K.act_c = c->d_a.p;
-        K.seq_c = io->seq ? c->d_seq.p : nullptr;
-        K.map = c->v_map.p;
-        K.rank = c->v_rank.p;
-        K.off = c->d_off.p;
-        K.pad_out = c->d_out.p;
-        K.pad_flags = c->d_flags.p;
-        HIPCHK(c, owgs_launch_invoke_compact(&K, st));
-        rc = invoke_engine(c, n, io->seq != nullptr, io->seq_base);
-        if (rc) return engine_failed(rc);
-    }
-    // the inputs of stages 2 and 3 go up while the engine runs
-    if (c->large) HIPCHK(c, upload(c->v_act, io->action, N, st));
-    HIPCHK(c, upload(c->k_key, (const ulonglong2*)io->aid, N, st));
-    HIPCHK(c, upload(c->k_r0, io->ticket, N, st));
-    HIPCHK(c, upload(c->x_tl, (const long long*)io->time_limit_ms, N, st));
-    OwgsMsgArgs A{};
-    if (msgs) {
-        rc = msg_upload(c, msgs, need, mo->n_topics, mo->cap, A, st);
-        if (rc) return rc;
-    }
-    OwgsInvokeGate Q{};
-    Q.n = n;
-    Q.err = c->d_err.p;
-    Q.rank = c->v_rank.p;
-    Q.dec = c->d_out.p;
-    Q.dflags = c->d_flags.p;
-    Q.action = c->v_act.p;
-    Q.act_bb = c->d_act_bb.p;
-    Q.placed = c->p_placed.p;
-    Q.msg_inv = msgs ? c->p_minv.p : nullptr;
-    Q.hdr = hdr;
-    Q.out_inv = b_inv;
-    Q.out_ticket = b_tick;
-    Q.out_flags = b_flags;
-    Q.out_existed = b_ex;
-    HIPCHK(c, owgs_launch_invoke_gate(&Q, st));
-    // stage 2: setupActivation of the placed items, by item: the entry's invoker from the scattered decisions, the
-    // namespace the gate's
-    rc = track_device(c, n, c->k_key.p, c->v_act.p, c->k_act.p, c->k_r0.p, b_inv, c->x_tl.p, io->now_ms,
-                      c->p_placed.p, b_tick, b_ex, hdr + OWGS_PUB_CNT, st);
-    if (rc) return rc;
-    // stage 3: the messages of the placed items
-    if (msgs) {
-        A.invoker = c->p_minv.p;
-        A.aid = c->k_key.p;
-        rc = msg_queue(c, A, mo->n_topics, st);
-        if (rc) return rc;
-        HIPCHK(c, owgs_launch_publish_collect(hdr, c->m_bad.p, A.topic_start, mo->n_topics, A.out_off, n, st));
-    }
-    HIPCHK(c, hipMemcpyAsync(c->p_pin, c->p_blk.p, blk_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    ++waits;
-    gate_out();
-    out_summary[12] = waits;
-    const char* P = (const char*)c->p_pin + hdr_bytes;
-    const PublishBlock B{P + 16 * N, P + 20 * N, P + 25 * N, P + 26 * N};
-    return publish_tail(c, "invoke", n, B, io->out_invoker, io->out_flags, io->out_ticket, io->out_existed, msgs, mo,
-                        out_summary, st);
-}
-
 int owgs_resident_stats(owgs_ctx* c, int64_t* out, int32_t cap) {
     if (!c || cap < 0 || (cap > 0 && !out)) return OWGS_EINVAL;
     const int64_t v[5] = {c->res_n_calls, c->res_n_launches, c->res_n_bails, c->res_n_chained, c->res_alive ? 1 : 0};
@@ -5638,6 +3411,12 @@ int owgs_large_stats(owgs_ctx* c, int64_t* out, int32_t cap) {
     v[3 + OWGS_SEQ_NPATH] = c->q_resumes;
     for (int32_t i = 0; i < cap && i < 4 + OWGS_SEQ_NPATH; ++i) out[i] = v[i];
     return 4 + OWGS_SEQ_NPATH;
+}
+
+int owgs_live_resources(int64_t out[3]) {
+    if (!out) return OWGS_EINVAL;
+    for (int k = 0; k < 3; ++k) out[k] = live_resources[k].load(std::memory_order_relaxed);
+    return OWGS_OK;
 }
 
 int owgs_engine_ms(owgs_ctx* c, float* ms) {

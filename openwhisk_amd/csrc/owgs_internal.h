@@ -1,4 +1,5 @@
-// owgs_internal.h -- device-side data layout shared by owgs_kernels.hip and owgs_host.cpp.
+// owgs_internal.h -- device-side data layout shared by the kernels (owgs_*.hip) and the host runtime (owgs_ctx.h,
+// owgs_host*.cpp); the launch wrappers between the two are declared in owgs_launch.h.
 //
 // HBM layout of one controller shard (one owgs_ctx), all struct-of-arrays:
 //   permits[n_slots]        i32  ForcibleSemaphore state of NestedSemaphore #i (indexed by invoker id, SCPB:413)

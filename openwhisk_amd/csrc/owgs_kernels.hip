@@ -35,6 +35,7 @@
 #include <atomic>
 
 #include "owgs_internal.h"
+#include "owgs_launch.h"
 #include "owgs_table.h"
 
 // Engine geometry variants (owgs_engine_narrow.hip): the same source compiled again with narrower chunks inside its own

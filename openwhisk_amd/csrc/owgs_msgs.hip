@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "owgs_internal.h"
+#include "owgs_launch.h"
 
 #define F_BLOCKING 1
 #define F_EXTRA 2

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "owgs_internal.h"
+#include "owgs_launch.h"
 #include "owgs_table.h"
 
 typedef unsigned long long u64;

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "owgs_internal.h"
+#include "owgs_launch.h"
 
 typedef unsigned long long u64;
 

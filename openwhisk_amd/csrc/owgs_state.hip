@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "owgs_internal.h"
+#include "owgs_launch.h"
 
 #define CP_TPB 1024
 #define CP_MAX 524287  // LDS flag bits (64 KB): the on-chip engines take pools up to 32767 positions, the large-state

@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "owgs_internal.h"
+#include "owgs_launch.h"
 #include "owgs_table.h"
 
 // ------------------------------------------------------------------------------------------------ reset

@@ -22,7 +22,7 @@ def test_header_declares_the_boundary():
     fns = ow.header_functions()
     for required in ["owgs_create", "owgs_destroy", "owgs_update_invokers", "owgs_update_cluster",
                      "owgs_register_actions", "owgs_publish_batch", "owgs_release_batch", "owgs_schedule_walks",
-                     "owgs_replay_device", "owgs_last_error"]:
+                     "owgs_replay_device", "owgs_last_error", "owgs_live_resources"]:
         assert required in fns
 
 

@@ -65,6 +65,20 @@ class Ctx:
             b.set_root_controller(RCI)
             assert b.register_namespaces([0xC0DE << 64 | k for k in range(5)]).tolist() == self.ns.tolist()
 
+    @classmethod
+    def around(cls, b, st, hs, actions, limits=(3, 3, 2), cluster=1):
+        """The model beside a balancer b and its oracle state st that already hold invokers and the actions `hs`
+        (tests/test_gpu_lifetime.py): sets up b's message and throttle state as the constructor does."""
+        self = cls.__new__(cls)
+        self.st, self.b, self.hs, self.ns = st, b, list(hs), np.arange(5, dtype=np.int32)
+        self.m = InvokeModel(PublishModel(st, dict(zip(self.hs, actions)), H), limits, cluster)
+        b.set_health_tid(H)
+        b.set_throttle_limits(*limits)
+        assert b.register_templates(TA, TB) == 0
+        b.set_root_controller(RCI)
+        assert b.register_namespaces([0xC0DE << 64 | k for k in range(5)]).tolist() == self.ns.tolist()
+        return self
+
 
 class Batch:
     """n items.  reject: positions that are rate-rejected for certain (rate override 0: limit 0).  forced: every other
@@ -137,7 +151,7 @@ def check_sweep(cx, now, twin=None):
     return got
 
 
-def run(cx, B, now, seq=None, seq_base=0, twin=None, waits=1):
+def run(cx, B, now, seq=None, seq_base=0, twin=None, waits=1, n_topics=N_TOPICS):
     """One call on the model, the device and (optionally) the twin context's separate calls; everything must agree.
     Returns the device's outputs."""
     want = cx.m.invoke(B.ns, B.kind, B.t, B.acts, B.aids, B.tks, B.lims, now, B.ro, B.co, seq, seq_base)
@@ -145,10 +159,10 @@ def run(cx, B, now, seq=None, seq_base=0, twin=None, waits=1):
     M = B.M
     wmsg = O.serialize_activations(TA, TB, RCI, np.where(want[5] >= 0, want[5], -1).astype(np.int32), M["tmpl"], words,
                                    M["tids"], M["tid_start"], M["flags"], M["contents"], M["causes"], M["traces"],
-                                   n_topics=N_TOPICS)
+                                   n_topics=n_topics)
     got = cx.b.invoke_activations(B.ns, B.kind, B.t, B.acts, B.aids, B.tks, B.lims, now, rate_override=B.ro,
                                   conc_override=B.co, seq=seq, seq_base=seq_base,
-                                  msgs=dict(M, n_topics=N_TOPICS, cap=len(wmsg[0])))
+                                  msgs=dict(M, n_topics=n_topics, cap=len(wmsg[0])))
     names = ("verdict", "rate_count", "rate_limit", "conc_count", "conc_limit", "invoker", "flags", "ticket", "existed")
     for k, name in enumerate(names):
         assert np.array_equal(got[k], want[k]), name
@@ -169,7 +183,7 @@ def run(cx, B, now, seq=None, seq_base=0, twin=None, waits=1):
         if len(adm):
             p = tb.publish_activations(B.acts[adm], [B.aids[i] for i in adm], B.tks[adm], B.lims[adm], now,
                                        ns=B.ns[adm], seq=None if seq is None else np.asarray(seq, np.uint64)[adm],
-                                       seq_base=seq_base, msgs=dict(B.sub_msgs(adm), n_topics=N_TOPICS,
+                                       seq_base=seq_base, msgs=dict(B.sub_msgs(adm), n_topics=n_topics,
                                                                     cap=len(wmsg[0])))
             for k in range(4):
                 assert np.array_equal(p[k], got[5 + k][adm]), names[5 + k]
