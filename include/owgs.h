@@ -87,7 +87,10 @@ int owgs_abi_version(void);
  * check it again before their first barrier (a mismatch fails the call with OWGS_EDEVICE, "engine geometry").
  * OWGS_OK when every wrapper refused. */
 int owgs_geometry_selfcheck(void);
-/* max invokers / slots the engine holds on chip (LDS); larger pools return OWGS_ERANGE from update_invokers */
+/* max invokers / slots the engine holds on chip (LDS); beyond them the large-state engine runs the context (DESIGN.md
+ * section 9), as it does one that has both a slot of 2^22 MB or more and a memory limit above 4095 MB: the on-chip
+ * engine's capacities floor(permits / mem) are exact below either bound (csrc/owgs_divq.h), and it refuses a state
+ * beyond both (OWGS_ERANGE).  States no engine holds return OWGS_ERANGE from update_invokers. */
 int owgs_limits(int32_t* max_invokers, int32_t* max_slots);
 
 /* Replaces: ShardingContainerPoolBalancerState.updateInvokers(newInvokers: IndexedSeq[InvokerHealth]) (SCPB:512-551),

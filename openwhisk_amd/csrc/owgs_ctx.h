@@ -390,6 +390,9 @@ struct owgs_ctx {
     // large-state engine (owgs_seq.hip): a state beyond every on-chip geometry (owgs_limits) or maxConcurrent beyond
     // OWGS_MAX_CONC runs there -- permits in HBM, the NestedSemaphore maps in one HBM table q_map
     bool large = false, big_conc = false;
+    // the chunked engine's capacities (owgs_divq.h) are exact while every slot is below 2^22 MB or every memory limit
+    // at most OWGS_DIVQ_MEM_ANY MB: a context that has seen both (sticky) runs on the large-state engine as well
+    bool wide_slots = false, wide_mem = false;
     DevBuf<uint4> q_map;
     int32_t q_cap = 0;
     DevBuf<int32_t> q_filled, q_state, q_look;

@@ -6,6 +6,7 @@
 // activation (slot permits, concurrency maps, outputs) lives in HBM and is updated by the HIP engine
 // (owgs_kernels.hip).  No CPU fallback exists: without a HIP device every compute entry point fails.
 #include "owgs_ctx.h"
+#include "owgs_divq.h"
 
 static int32_t d2i(double d) {  // Scala Double.toInt
     if (d != d) return 0;
@@ -385,7 +386,7 @@ void base_args(owgs_ctx* c, OwgsEngineArgs& A) {
     A.rng_seed = c->cfg.rng_seed;
     A.stats = c->d_stats.p;
     A.err = c->d_err.p;
-    A.opts = env_opts().opts;
+    A.opts = (env_opts().opts & ~OWGS_OPT_WIDE_MEM) | (c->wide_mem ? OWGS_OPT_WIDE_MEM : 0);
     A.hwords = c->grp_hwords;
     A.hstride = c->grp_hstride;
     A.trace = nullptr;
@@ -579,7 +580,8 @@ int check_err_word(owgs_ctx* c) {
         if (e & OWGS_ERR_OPS) return c->fail(OWGS_ERANGE, "operationCount beyond the engine's range");
         if (e & OWGS_ERR_GEOM) return c->fail(OWGS_EDEVICE, "engine object and host disagree on the engine geometry");
         if (e & OWGS_ERR_INTERNAL) return c->fail(OWGS_EDEVICE, "engine invariant violated");
-        if (e & OWGS_ERR_PERMITS) return c->fail(OWGS_ERANGE, "slot permits outside the engine's range [-2^29, 2^29) MB");
+        if (e & OWGS_ERR_PERMITS)
+            return c->fail(OWGS_ERANGE, "slot permits outside the engine's range [-2^29, 2^29) MB (2^22 with memory limits above 4095 MB)");
         if (e & OWGS_ERR_RELRISK)  // (stream mode only: the chunked engine applies such releases and flags FS:48-50)
             return c->fail(OWGS_ERANGE, "stream-mode replay stopped before a release that could overflow a slot's "
                                         "permits (ForcibleSemaphore.release FS:48-50): the rest of the stream is not "
@@ -1042,6 +1044,13 @@ static bool large_fits(int32_t n_ids, int32_t nm, int32_t nb) {
     return n_ids <= OWGS_SEQ_MAX_WORDS * 32 && nm <= owgs_coprime_max() && nb <= owgs_coprime_max();
 }
 
+// whether an invoker's slot can leave the domain in which the chunked engine's capacity form is exact for every
+// memory limit (owgs_divq.h).  By its whole memory, the slot of a cluster of one (getInvokerSlot, SCPB:490-497): no
+// cluster size gives a larger one, so owgs_update_cluster never has to move a context
+static bool slot_is_wide(const owgs_ctx* c, int64_t mem_bytes) {
+    return std::max<int64_t>(mem_bytes, c->cfg.min_memory_bytes) / (1024 * 1024) >= (int64_t)OWGS_DIVQ_XMAX;
+}
+
 OwgsSeqArgs seq_args(owgs_ctx* c) {
     OwgsSeqArgs S{};
     S.permits = c->d_permits.p;
@@ -1260,7 +1269,9 @@ int owgs_geometry_selfcheck(void) {
 
 int owgs_limits(int32_t* max_invokers, int32_t* max_slots) {
     // identity pools (the largest on-chip state per invoker: permits + usable bit + prefix counts): the largest
-    // invoker count whose LDS image fits, found by bisection over the layout itself
+    // invoker count whose LDS image fits, found by bisection over the layout itself.  (Counts only: a context within
+    // them still leaves the chip when it has both a slot of 2^22 MB or more and a memory limit above
+    // OWGS_DIVQ_MEM_ANY MB, slot_is_wide / wide_mem below.)
     int32_t lo = 0, hi = OWGS_MAX_SLOTS_CT;
     while (lo < hi) {
         const int32_t mid = lo + (hi - lo + 1) / 2;
@@ -1337,7 +1348,7 @@ int owgs_update_invokers(owgs_ctx* c, int32_t n, const int32_t* ids, const int64
     }
     const int32_t old_size = (int32_t)c->ids.size();
     const int32_t new_size = n;
-    bool large_next = false;
+    bool large_next = false, wide_next = c->wide_slots;
     int32_t managed = d2i(std::ceil((double)new_size * c->mf));
     if (managed < 1) managed = 1;
     int32_t blackboxes = d2i(std::floor((double)new_size * c->bf));
@@ -1350,7 +1361,10 @@ int owgs_update_invokers(owgs_ctx* c, int32_t n, const int32_t* ids, const int64
         for (int32_t i = 0; identity && i < n; ++i) identity = ids[i] == i;
         // (a context already on the large-state engine stays there: its NestedSemaphore map lives in that layout;
         // slots never shrink, so a pool that left the chip cannot fit it again anyway)
-        large_next = c->large || c->big_conc ||
+        // (a slot of 2^22 MB or more beside a memory limit above OWGS_DIVQ_MEM_ANY MB: outside the on-chip
+        // capacity form's domain)
+        for (int32_t i = 0; i < n && !wide_next; ++i) wide_next = slot_is_wide(c, user_memory_bytes[i]);
+        large_next = c->large || c->big_conc || (wide_next && c->wide_mem) ||
                      engine_variant(slots, identity ? 0 : 1, n, std::min(managed, n), std::min(blackboxes, n)) < 0;
         if (large_next && !(identity && large_fits(n, std::min(managed, n), std::min(blackboxes, n))))
             return c->fail(OWGS_ERANGE, "invoker state exceeds every engine (owgs_limits; explicit pools on chip only)");
@@ -1401,6 +1415,7 @@ int owgs_update_invokers(owgs_ctx* c, int32_t n, const int32_t* ids, const int64
         }
     }
     const bool was_large = c->large;
+    c->wide_slots = wide_next;
     c->large = large_next || c->big_conc;
     int rc = rebuild_pools(c);
     if (!rc && c->large && !was_large) rc = seq_migrate(c);
@@ -1458,6 +1473,9 @@ int owgs_register_actions(owgs_ctx* c, int32_t n, const char* ns_bytes, const in
         // beyond the on-chip map's field: the large-state engine, which walks identity pools only
         if (max_conc[i] > OWGS_MAX_CONC && !c->big_conc && !c->ids.empty() && c->pool_mode != 0)
             return c->fail(OWGS_ERANGE, "maxConcurrent beyond 4095 needs identity pools");
+        // beyond the on-chip capacity form's domain (owgs_divq.h): the large-state engine as well
+        if (mem_mb[i] > OWGS_DIVQ_MEM_ANY && c->wide_slots && !c->large && c->pool_mode != 0)
+            return c->fail(OWGS_ERANGE, "memory limits above 4095 MB beside slots of 2^22 MB and more need identity pools");
     }
     // handles: released ones first, then new ids below OWGS_REC_NOACT
     if ((size_t)n > c->free_handles.size() + ((size_t)OWGS_REC_NOACT - c->a_mem.size()))
@@ -1543,10 +1561,12 @@ int owgs_register_actions(owgs_ctx* c, int32_t n, const char* ns_bytes, const in
         c->a_live[a] = 1;
         if (max_conc[i] > 1) c->any_conc = true;
         if (max_conc[i] > OWGS_MAX_CONC) c->big_conc = true;  // (checked above: identity pools)
+        if (mem_mb[i] > OWGS_DIVQ_MEM_ANY) c->wide_mem = true;
         hid[i] = a;
         out_action[i] = a;
     }
-    if (c->big_conc && !c->large) {  // beyond the on-chip map's field: move the slot state to the large-state engine
+    // beyond the on-chip map's field, or the on-chip capacity form's domain: move the slot state to the large-state engine
+    if ((c->big_conc || (c->wide_mem && c->wide_slots)) && !c->large) {
         c->large = true;
         const int rm = seq_migrate(c);
         if (rm) return rm;
@@ -1793,6 +1813,8 @@ int owgs_schedule_walks(owgs_ctx* c, int32_t n, const uint8_t* pool, const int32
     OwgsEngineArgs A;
     base_args(c, A);
     A.feat = OWGS_F_ALL;  // explicit walks carry their own limits
+    for (int32_t i = 0; i < n; ++i)
+        if (mem_mb[i] > OWGS_DIVQ_MEM_ANY) A.opts |= OWGS_OPT_WIDE_MEM;  // (the engine then refuses a slot of 2^22 MB)
     A.seq = seq ? c->d_seq.p : nullptr;
     A.out_inv = c->d_out.p;
     A.out_flags = c->d_flags.p;
@@ -1814,6 +1836,11 @@ int owgs_set_slots(owgs_ctx* c, int32_t n, const int32_t* permits) {
         const int ro_ = order_on(c, c->stream);
         if (ro_) return ro_;
     }
+    bool wide = false;
+    for (int32_t i = 0; i < n && !wide; ++i) wide = permits[i] >= OWGS_DIVQ_XMAX;
+    if (wide && c->wide_mem)  // (explicit slots live on chip only)
+        return c->fail(OWGS_ERANGE, "slots of 2^22 MB and more beside memory limits above 4095 MB: large-state engine only");
+    c->wide_slots = c->wide_slots || wide;
     int rw = w_rebuild(c);
     if (rw) return rw;
     HIPCHK(c, upload(c->d_permits, permits, (size_t)n, c->stream));

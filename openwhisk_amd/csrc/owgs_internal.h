@@ -100,11 +100,17 @@
 #define OWGS_ERR_BAD_STREAM 2          // replay: a release without a matching acquire, or a permit overflow
 #define OWGS_ERR_OPS 4
 #define OWGS_ERR_INTERNAL 8             // engine invariant violated (a pass without progress)
-#define OWGS_ERR_PERMITS 16             // slot permits outside [-2^29, 2^29) MB (the LDS encoding's range)
+#define OWGS_ERR_PERMITS 16             // slot permits outside [-2^29, 2^29) MB (the LDS encoding's range), or of 2^22 MB
+                                        // and more in a launch with OWGS_OPT_WIDE_MEM (the capacity form's domain)
 #define OWGS_ERR_GEOM 32                // the launch's geometry tag is not the engine object's (nothing was touched)
 #define OWGS_ERR_RELRISK 64             // owgs_process_batch: the call's releases could push a slot's permits out of the
                                         // LDS range; the engine returned before touching anything (the host reruns the
                                         // call through the ordered release kernels)
+
+// OwgsEngineArgs.opts: the launch may carry memory limits above OWGS_DIVQ_MEM_ANY MB (owgs_divq.h), so every permit
+// count has to stay below 2^22 MB for the engine's capacities to be exact; the host sends a context with such limits
+// and such a slot to the large-state engine
+#define OWGS_OPT_WIDE_MEM 2
 
 // LDS permits of identity pools carry the usable flag: an unusable invoker's permits are stored + OWGS_PENC, so one
 // LDS read gives both (usable permits < OWGS_PLIM <= unusable ones); HBM holds the plain values
@@ -191,7 +197,7 @@ struct OwgsEngineArgs {
     unsigned long long* stats;   // this launch's counters (zero when it starts)
     unsigned long long* stats_next;  // the next launch's counter block: zeroed at the end of this one (no fill launch)
     int32_t* err;
-    int32_t opts;                // diagnostics (env OWGS_OPTS): bit0 = no hot-action rank tables
+    int32_t opts;                // bit0 (diagnostics, env OWGS_OPTS) = no hot-action rank tables; OWGS_OPT_WIDE_MEM
     int32_t cw;                  // chunk width of this replay (<= OWGS_WL)
     unsigned long long* trace;   // diagnostic build only (-DOWGS_TRACE): [waves][OWGS_TRACE_CAP] barrier timeline
     int32_t feat;                // engine code paths this launch needs (OWGS_F_*): picks the compiled specialisation

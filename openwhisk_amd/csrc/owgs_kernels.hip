@@ -34,6 +34,7 @@
 
 #include <atomic>
 
+#include "owgs_divq.h"
 #include "owgs_internal.h"
 #include "owgs_launch.h"
 #include "owgs_table.h"
@@ -88,6 +89,9 @@ typedef unsigned long long u64;
 #endif
 #ifndef OWGS_COOP_CLASH
 #define OWGS_COOP_CLASH 1  // after the re-decisions the lanes that stay test themselves against the re-decided sets (0: the I/O wave marks them in fxa)
+#endif
+#ifndef OWGS_DIVQ
+#define OWGS_DIVQ 1  // walk arithmetic by the exact forms of owgs_divq.h (0: float reciprocal plus correction chains)
 #endif
 #ifndef EXT_MAX
 #define EXT_MAX 48  // re-decisions per pass
@@ -405,6 +409,63 @@ __device__ __forceinline__ int cap_bf(int pv, int m, float rm) {
     q -= r < 0 ? 1 : 0;
     q = min(q, CAPMAX);
     return pv >= m ? q : 0;
+}
+
+// The walk arithmetic of the chunked engine.  OWGS_DIVQ = 1: the exact forms of owgs_divq.h, whose
+// per-divisor constants are computed where the divisor is fixed (the lane decode, the kernel prologue); 0: the forms
+// above, which need none.  DivCap: capacities by one memory limit; DivPos: positions in one pool.
+struct DivCap {
+    int m;
+    float rm, hrm;
+};
+struct DivPos {
+    int n;
+    uint32_t M;
+};
+__device__ __forceinline__ DivCap div_cap_of(int m, float rm) { return DivCap{m, rm, 0.5f * rm}; }
+// the reciprocal a DivCap needs: correctly rounded (OWGS_DIVQ), or the hardware's estimate
+__device__ __forceinline__ float div_rm(int m) {
+#if OWGS_DIVQ
+    return owgs_divq_rm(m);
+#else
+    return __builtin_amdgcn_rcpf((float)m);
+#endif
+}
+__device__ __forceinline__ DivCap div_cap(int m) { return div_cap_of(m, div_rm(m)); }
+// min(floor(pv / m), CAPMAX), 0 for pv < m (negative permits included); usable permits are below 2^22
+__device__ __forceinline__ int cap_q(int pv, const DivCap& d) {
+#if OWGS_DIVQ
+    return owgs_divq_cap(pv, d.rm, d.hrm, CAPMAX);
+#else
+    return cap_bf(pv, d.m, d.rm);
+#endif
+}
+// the general walk's capacity (pv < OWGS_PLIM): the same value; the old form branches
+__device__ __forceinline__ int cap_g(int pv, const DivCap& d) {
+#if OWGS_DIVQ
+    return cap_q(pv, d);
+#else
+    return cap_of(pv, d.m, d.rm);
+#endif
+}
+__device__ __forceinline__ DivPos div_pos(int n, uint32_t M) { return DivPos{n, M}; }
+// x mod n for 0 <= x < 2^31, 1 <= n < 2^15
+__device__ __forceinline__ int pos_mod(int x, const DivPos& d) {
+#if OWGS_DIVQ
+    return owgs_divq_mod(x, d.n, d.M);
+#else
+    return mod_fast(x, d.n, __builtin_amdgcn_rcpf((float)d.n));
+#endif
+}
+// x mod n for ranks (< 2^10) against maxConcurrent (< 2^12): owgs_divq.h's small remainder takes the hardware's
+// reciprocal estimate, so no division per lane
+static_assert(CAPMAX == OWGS_DIVQ_CAPMAX && OWGS_MAX_MEM_MB == OWGS_DIVQ_MAX_MEM, "owgs_divq.h mirrors the engine's bounds");
+__device__ __forceinline__ int small_mod(int x, int n) {
+#if OWGS_DIVQ
+    return owgs_divq_small_mod(x, n, __builtin_amdgcn_rcpf((float)n));
+#else
+    return mod_fast(x, n, __builtin_amdgcn_rcpf((float)n));
+#endif
 }
 
 // LDS-DMA (global_load_lds): each lane's 16 (4) bytes land at lds_dst + 16 (4) * lane.  M0 is compiler-reserved:
@@ -1206,6 +1267,15 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
     const int tid = threadIdx.x, wave = IO ? OWGS_EW : tid >> 6, lane = tid & 63;
     constexpr bool io = IO;
     const int n_slots = A.n_slots, nm = A.nm, nb = A.nb;
+    // positions in the two pools: their multipliers, once per launch (nobody walks an empty pool).  They live in
+    // vector registers, of which the kernel has some to spare: as scalars they would be two more values spilled to
+    // VGPR lanes and read back at every use
+    uint32_t mgm = OWGS_DIVQ ? owgs_divq_magic((uint32_t)max(nm, 1)) : 0u;
+    uint32_t mgb = OWGS_DIVQ ? owgs_divq_magic((uint32_t)max(nb, 1)) : 0u;
+#if OWGS_DIVQ
+    asm volatile("" : "+v"(mgm), "+v"(mgb));
+#endif
+    const DivPos dvm = div_pos(nm, mgm), dvb = div_pos(nb, mgb);
     const int words = (A.n_ids + 31) >> 5;
 
     // ---------------------------------------------------------------- state -> LDS
@@ -1214,7 +1284,11 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
     if (tid < SC_N)
         sc[tid] = (tid == SC_IRR || tid == SC_RRISK) ? 0
                                                      : ((tid < 4 || tid >= SC_CFT) ? OWGS_WL : (tid < 6 ? (int)0x80000000 : 0));
-    if (A.rel_bound) lds_sync();  // (SC_RRISK is set below)
+    // the capacity form's domain (owgs_divq.h): permits below 2^22 MB, or memory limits of at most
+    // OWGS_DIVQ_MEM_ANY MB (every larger quotient is clamped).  The host keeps states with both off this engine; one
+    // that arrives all the same is refused before anything is touched (OWGS_ERR_PERMITS)
+    const bool wide_mem = OWGS_DIVQ && (A.opts & OWGS_OPT_WIDE_MEM) != 0;  // (uniform)
+    if (A.rel_bound || wide_mem) lds_sync();  // (SC_RRISK is set below)
     bool rrisk = false;    // (owgs_process_batch) a slot the call's releases could push out of the LDS range
     // permits four slots per 16-byte load, with their usable word and (owgs_process_batch) their release bounds, all
     // issued before any is used: one round trip per 10,240 slots (the headline's state in one)
@@ -1259,17 +1333,24 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
         P[i] = slot_in(i, A.permits[i], (pool_mode == 0 && i < A.n_ids) ? A.usable[i >> 5] : ~0u, bnd);
         if (bnd) A.rel_bound[i] = 0ull;
     }
-    if (rrisk) sc[SC_RRISK] = 1;
+    if (rrisk) atomicOr(&sc[SC_RRISK], 1);
+    if (wide_mem) {  // (rare: a pass of its own over the permits keeps the common load lean)
+        bool pdom = false;
+        for (int i = tid; i < n_slots; i += OWGS_NT) pdom = pdom || A.permits[i] >= OWGS_DIVQ_XMAX;
+        if (pdom) atomicOr(&sc[SC_RRISK], 2);
+    }
     if (pool_mode == 0) {
         for (int i = tid; i < words; i += OWGS_NT) ub[i] = A.usable[i];
     } else {
         for (int i = tid; i < nm + nb; i += OWGS_NT) pw[i] = (int16_t)A.pool_words[i];
     }
     lds_sync();
-    // releases that could leave the range: nothing has been written yet -- the host replays the call through the
-    // ordered release kernels (which flag ForcibleSemaphore's overflow Error per release, FS:48-50)
-    if (A.rel_bound && sc[SC_RRISK]) {  // (uniform)
-        if (tid == 0) tail_early(OWGS_ERR_RELRISK);
+    // releases that could leave the range: no state has been written yet (only the staged release bounds were
+    // consumed, which every call stages anew) -- the host replays the call through the ordered release kernels (which
+    // flag ForcibleSemaphore's overflow Error per release, FS:48-50); a state outside the capacity form's domain
+    // fails the call
+    if ((A.rel_bound || wide_mem) && sc[SC_RRISK]) {  // (uniform)
+        if (tid == 0) tail_early((sc[SC_RRISK] & 2) ? OWGS_ERR_PERMITS : OWGS_ERR_RELRISK);
         if (A.stats_next && tid < OWGS_NSTATS) A.stats_next[tid] = 0ull;
         return;
     }
@@ -1709,7 +1790,9 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
             for (int i = tid; i < n_slots; i += OWGS_ENT) {
                 const int v = P[i];
                 const bool unusable = pool_mode == 0 && i < A.n_ids && !((ub[i >> 5] >> (i & 31)) & 1u);
-                if ((unusable ? v - OWGS_PENC : v) >= OWGS_PLIM) err |= OWGS_ERR_PERMITS;
+                const int pvv = unusable ? v - OWGS_PENC : v;
+                if (pvv >= OWGS_PLIM || (OWGS_DIVQ && (A.opts & OWGS_OPT_WIDE_MEM) && pvv >= OWGS_DIVQ_XMAX))
+                    err |= OWGS_ERR_PERMITS;
             }
             int m0 = (int)0x80000000, m1 = (int)0x80000000;
             if (pool_mode == 0) {
@@ -1776,7 +1859,8 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
             const int ext = (int)((rc4.z >> 27) | ((rc4.w >> 27) << 5));  // pk1 (maxConc > 1) or hot slot
             const int pk1 = (maxc > 1 && ext < HOT_CONC) ? ext : 0;
             const int n = pool ? nb : nm;
-            const float rm = __builtin_amdgcn_rcpf((float)(mem > 0 ? mem : 1));
+            const DivPos dvn = pool ? dvb : dvm;
+            const DivCap dcm = div_cap(mem > 0 ? mem : 1);  // (the lane's memory limit is fixed for the chunk)
             const int64_t i = c0 + li;
             bool pending = valid;
             TRACE_MARK(7);
@@ -1801,7 +1885,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                 const int inv = t0 < 0 ? t0 + n : t0;
                 const int d = xp - home;
                 const int dd = d < 0 ? d + n : d;
-                return (uint32_t)(int)(((long long)dd * inv) % n);
+                return (uint32_t)pos_mod(dd * inv, dvn);  // (dd, inv < n < 2^15)
             };
             // chunk cursor word of each action, at its first lane: walk step (15 bits) | lanes committed (10 bits);
             // the step starts from the action's HBM cursor when it was written in this batch (a lower bound: steps
@@ -1822,7 +1906,8 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
             const int hs = (valid && hsx >= 0 && hsx < NHOT && !(A.opts & 1)) ? hsx : -1;
             if (hs >= 0) {
                 if (occ == 0) {
-                    hdir[hs] = make_uint4((uint32_t)li, rc4.x, rc4.y, (uint32_t)slot);  // .x = cursor word
+                    // .x = the memory limit's reciprocal, .w = slot | cursor word (the first lane) << 17
+                    hdir[hs] = make_uint4(__float_as_uint(dcm.rm), rc4.x, rc4.y, (uint32_t)slot | ((uint32_t)li << 17));
                     hflag[hs] = 0;  // walked in the first pass (f = 0)
                     atomicMax(&sc[SC_NHOT], hs + 1);
                 }
@@ -1899,8 +1984,8 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                         const bool hcok = (d.y & OWGS_AM_COK) != 0;
                         const int hmem = (int)(d.z & OWGS_AM_MEM_MASK);
                         const int hmc = conc_of(d.z);
-                        const int hslot = (int)d.w;
-                        const uint32_t hcw = ccw[d.x];
+                        const int hslot = (int)(d.w & 0x1FFFFu);
+                        const uint32_t hcw = ccw[d.w >> 17];
                         const int hcc = (int)((hcw >> 15) & OWGS_RMASK);
                         const int need = min(hocc[h] - hcc + 1, HOT_RANKS);
                         if (need <= 0) continue;
@@ -1911,10 +1996,10 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                             continue;
                         }
                         int s0 = hcok ? (int)(hcw & 0x7FFFu) : 0;
-                        const float rnn = __builtin_amdgcn_rcpf((float)hn);
-                        int p0 = mod_fast(hhome + s0 * hstep, hn, rnn);
-                        const int loff = mod_fast(lane * hstep, hn, rnn), boff = mod_fast(64 * hstep, hn, rnn);
-                        const float rmh = __builtin_amdgcn_rcpf((float)hmem);
+                        const DivPos dvh = hpool ? dvb : dvm;
+                        int p0 = pos_mod(hhome + s0 * hstep, dvh);
+                        const int loff = pos_mod(lane * hstep, dvh), boff = pos_mod(64 * hstep, dvh);
+                        const DivCap dch = div_cap_of(hmem, __uint_as_float(d.x));
                         int* scr = hscr + wave * 64;
                         int cum = 0;
                         ++st_long;
@@ -1939,11 +2024,11 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                     bad = true;
                                 } else if (id >= 0) {
                                     if (hmc == 1) {
-                                        cap = cap_bf(pv, hmem, rmh);
+                                        cap = cap_q(pv, dch);
                                     } else {
                                         uint32_t v;
                                         ct_find2(ct, A.ovf, ovf_on, ct_key(id, hslot), &v);
-                                        cap = (int)(v & OWGS_CT_C_MASK) + min(cap_bf(pv, hmem, rmh) * hmc, CAPMAX);
+                                        cap = (int)(v & OWGS_CT_C_MASK) + min(cap_q(pv, dch) * hmc, CAPMAX);
                                     }
                                 }
                             }
@@ -2004,10 +2089,10 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                         } else if (OWGS_CSCAN_ON && maxc > 1 && mem > U && pool_mode == 0 && n > OWGS_CSCAN_MIN_N && !ovf_on) {
                             kind = K_CSCAN;  // no invoker can open a container: capacity = the key's open ones
                             ws = s;          // (the ordinary walk's start, should the key have > 64 of them)
-                            wpos = mod_fast(home + s * step, n, __builtin_amdgcn_rcpf((float)n));
+                            wpos = pos_mod(home + s * step, dvn);
                             wcum = 0;
                         } else {
-                            int pos = mod_fast(home + s * step, n, __builtin_amdgcn_rcpf((float)n));
+                            int pos = pos_mod(home + s * step, dvn);
                             int cum = 0;
                             kind = K_LONG;
 #ifdef OWGS_PROFILE
@@ -2042,7 +2127,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                     bool ended = false;
 #pragma unroll
                                     for (int k = 0; k < FGRP; ++k) {
-                                        const int cap = pv[k] < OWGS_PLIM ? cap_bf(pv[k], mem, rm) : 0;
+                                        const int cap = pv[k] < OWGS_PLIM ? cap_q(pv[k], dcm) : 0;
                                         const bool open = hit == FGRP && !ended;
                                         const bool fin = open && s + k >= n;
                                         const bool h = open && !fin && kc + cap > r;
@@ -2119,7 +2204,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
 #endif
                                         }
                                         const int cap = pv[k] < OWGS_PLIM
-                                                            ? (int)(v & OWGS_CT_C_MASK) + min(cap_bf(pv[k], mem, rm) * maxc, CAPMAX)
+                                                            ? (int)(v & OWGS_CT_C_MASK) + min(cap_q(pv[k], dcm) * maxc, CAPMAX)
                                                             : 0;
                                         const bool h = open && !fin && kc + cap > r;
                                         ended = ended || fin;
@@ -2168,11 +2253,11 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                 if (id >= 0) {
                                     int cap;
                                     if (maxc == 1) {
-                                        cap = cap_of(pv, mem, rm);
+                                        cap = cap_g(pv, dcm);
                                     } else {
                                         uint32_t v;
                                         const int ci = ct_find2(ct, A.ovf, ovf_on, ct_key(id, slot), &v);
-                                        cap = (int)(v & OWGS_CT_C_MASK) + min(cap_of(pv, mem, rm) * maxc, CAPMAX);
+                                        cap = (int)(v & OWGS_CT_C_MASK) + min(cap_g(pv, dcm) * maxc, CAPMAX);
                                         if (cum + cap > r) {
                                             cval = v;
                                             cidx = ci;
@@ -2271,7 +2356,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                 r1 = rr;
                             }
                             const int sinv = t0 < 0 ? t0 + nn : t0;
-                            const float rnn = __builtin_amdgcn_rcpf((float)nn);
+                            const DivPos dvc = pj ? dvb : dvm;
                             if (lane < nc) {
                                 ix = cand[lane];
                                 const uint2 ev = ct[ix];
@@ -2280,7 +2365,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                 cx = (int)(vx & OWGS_CT_C_MASK);
                                 int d = idv - base - hj;
                                 d += d < 0 ? nn : 0;
-                                kx = mod_fast(d * sinv, nn, rnn);  // d, sinv < n < 2^15
+                                kx = pos_mod(d * sinv, dvc);  // d, sinv < n < 2^15
                             }
                             // free slots of the containers before this one in walk order (distinct steps)
                             for (int m2 = 0; m2 < nc; ++m2) {
@@ -2342,8 +2427,9 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                         if (spec && kind == K_LONG) {
                             lq_i = qb + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32),
                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
-                            lq[lq_i] = make_uint4((uint32_t)sl | ((uint32_t)r << 16), (uint32_t)ws, (uint32_t)wpos,
-                                                  (uint32_t)wcum);
+                            // (walk step and position < 2^15 share a word; the memory limit's reciprocal rides along)
+                            lq[lq_i] = make_uint4((uint32_t)sl | ((uint32_t)r << 16), (uint32_t)ws | ((uint32_t)wpos << 16),
+                                                  (uint32_t)wcum, __float_as_uint(dcm.rm));
                         }
                     }
                 }
@@ -2371,9 +2457,9 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                         ++st_long;
                         const uint4 qe = lq[item];
                         const uint4 qr = stgA[sbuf * OWGS_WL + (int)(qe.x & 0xFFFFu)];
-                        int s0 = (int)qe.y;
-                        int p0 = (int)qe.z;
-                        int cum = (int)qe.w;
+                        int s0 = (int)(qe.y & 0xFFFFu);
+                        int p0 = (int)(qe.y >> 16);
+                        int cum = (int)qe.z;
                         const int rj = (int)(qe.x >> 16);
                         const int stp = (int)((qr.x >> 15) & OWGS_AM_POS_MASK);
                         const int pj = (qr.x & OWGS_AM_POOL) ? 1 : 0;
@@ -2381,13 +2467,13 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                         const int mj = (int)(qr.y & OWGS_AM_MEM_MASK);
                         const int cj = conc_of(qr.y);
                         const int slj = (int)(qr.w & 0x1FFFFu);
-                        const float rmj = __builtin_amdgcn_rcpf((float)mj);
-                        const float rnn = __builtin_amdgcn_rcpf((float)nn);
+                        const DivCap dcj = div_cap_of(mj, __uint_as_float(qe.w));
+                        const DivPos dvj = pj ? dvb : dvm;
                         // lane l probes steps l, 64 + l, .. of the round: each of its LW_Q reads is a stride-step
                         // gather over the wave (step sizes are odd: conflict-free over the LDS banks)
-                        const int loff = mod_fast(lane * stp, nn, rnn);
-                        const int boff = mod_fast(64 * stp, nn, rnn);
-                        const int roff = mod_fast(64 * LW_Q * stp, nn, rnn);
+                        const int loff = pos_mod(lane * stp, dvj);
+                        const int boff = pos_mod(64 * stp, dvj);
+                        const int roff = pos_mod(64 * LW_Q * stp, dvj);
                         int rk = K_FALLBACK, rt = -1, rks = 0, rst = 0, rci = -1;
                         uint32_t rcv = 0;
 #ifdef OWGS_PROFILE
@@ -2468,13 +2554,13 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                     continue;
                                 }
                                 if (cj == 1) {
-                                    cap = (in && id[q] >= 0) ? cap_bf(pv[q], mj, rmj) : 0;
+                                    cap = (in && id[q] >= 0) ? cap_q(pv[q], dcj) : 0;
                                 } else if (in && id[q] >= 0) {
                                     const uint32_t key = ct_key(id[q], slj);
                                     const int bst = ct_block(ea[q], eb[q], key, hx[q], &v, &ci);
                                     if (bst == 2 || (bst == 0 && ovf_on))
                                         ci = ct_resolve2(ct, A.ovf, ovf_on, bst, key, hx[q], &v, ci);
-                                    cap = (int)(v & OWGS_CT_C_MASK) + min(cap_bf(pv[q], mj, rmj) * cj, CAPMAX);
+                                    cap = (int)(v & OWGS_CT_C_MASK) + min(cap_q(pv[q], dcj) * cj, CAPMAX);
                                 }
                                 const int inc = wave_incl_scan(cap);
                                 const u64 hm = __ballot(in && (bad || cum + inc > rj));
@@ -2632,7 +2718,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                     const int c0v = (int)(cval & OWGS_CT_C_MASK);
                     if (maxc == 1) cons = mem;
                     else if (kind == K_FALLBACK) cons = c0v >= 1 ? 0 : mem;
-                    else cons = (ks < c0v) ? 0 : (mod_fast(ks - c0v, maxc, __builtin_amdgcn_rcpf((float)maxc)) == 0 ? mem : 0);
+                    else cons = (ks < c0v) ? 0 : (small_mod(ks - c0v, maxc) == 0 ? mem : 0);
                 }
                 // ------------------------------------------------ bucket totals
                 // every lane tentatively takes its memory from its target's permits: after the barrier P[t] is the
@@ -2730,7 +2816,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                         };
                         bmark(t);  // (a lane re-decided away from t leaves room there)
                         int s = s_t + 1;
-                        int pos = mod_fast(home + s * step, n, __builtin_amdgcn_rcpf((float)n));
+                        int pos = pos_mod(home + s * step, dvn);
                         bool found = false;
                         int tp = 0, sp = 0;
 #pragma unroll 1
@@ -2889,8 +2975,13 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                             // permits bound this lane's)
                             if (!done) done = mm > (pl_ ? u1 : u0) && ((A.shortcut_ok >> pl_) & 1);
                             if (!done) {
-                                const float rnn = __builtin_amdgcn_rcpf((float)nn);
+                                const DivPos dvx = pl_ ? dvb : dvm;
                                 int s0 = (int)(fy >> 16);
+#if OWGS_DIVQ
+                                // the round's first position is reduced once (one value for the wave); each lane adds
+                                // its own offset (and the second half-round's) with one conditional subtract
+                                const int loff = pos_mod(lane * st_, dvx), boff = pos_mod(64 * st_, dvx);
+#endif
                                 for (int rd = 0; rd < EXT_ROUNDS; ++rd) {
 #ifdef OWGS_EXT_PROF
                                     ++xp_rounds;
@@ -2900,8 +2991,16 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                         break;
                                     }
                                     // walk steps s0 + lane and s0 + 64 + lane ((s0 + 127) * step < 2^31)
-                                    const int xa = base + mod_fast(hm_ + (s0 + lane) * st_, nn, rnn);
-                                    const int xb = base + mod_fast(hm_ + (s0 + 64 + lane) * st_, nn, rnn);
+#if OWGS_DIVQ
+                                    int pa = pos_mod(hm_ + s0 * st_, dvx) + loff;
+                                    pa -= pa >= nn ? nn : 0;
+                                    int pb = pa + boff;
+                                    pb -= pb >= nn ? nn : 0;
+                                    const int xa = base + pa, xb = base + pb;
+#else
+                                    const int xa = base + pos_mod(hm_ + (s0 + lane) * st_, dvx);
+                                    const int xb = base + pos_mod(hm_ + (s0 + 64 + lane) * st_, dvx);
+#endif
                                     const bool ia = s0 + lane < nn, ib = s0 + 64 + lane < nn;
                                     const int va = ia ? P[xa] : OWGS_PENC, vb = ib ? P[xb] : OWGS_PENC;
                                     const bool fa = va < OWGS_PLIM && va >= mm;  // (usable: flag folded in)
@@ -3078,8 +3177,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                             const int c0v = (int)(cval & OWGS_CT_C_MASK), ops0 = ct_ops(cval);
                             const int jn = kind == K_FALLBACK ? 1 : ks + 1;
                             const int c1 = jn <= c0v ? c0v - jn
-                                                     : (maxc - 1 - mod_fast(jn - c0v - 1, maxc,
-                                                                            __builtin_amdgcn_rcpf((float)maxc)));
+                                                     : (maxc - 1 - small_mod(jn - c0v - 1, maxc));
                             const int ops1 = ops0 + jn;
                             if (ops1 > OWGS_MAX_OPS) err |= OWGS_ERR_OPS;
                             int ix = cidx;

@@ -7,9 +7,14 @@ compiler's resource-usage remark (SGPRs, VGPRs, spills, scratch).  Needs hipcc, 
 Each file is compiled three times: as the library builds it (both roles in one kernel), and with -DOWGS_ROLE_ONLY=0 /
 =1, which fixes the kernels' role branch to the engine waves' / the I/O wave's body, so the two paths can be read apart.
 
-    python tools/engine_isa.py [--src DIR] [--only-kernel SUBSTR] > profiles/engine_split_isa.txt
+    python tools/engine_isa.py [--src DIR] [--only-kernel SUBSTR] [--regions] > profiles/engine_split_isa.txt
 
 --src points at another checkout's openwhisk_amd/ (a parent build, which ignores OWGS_ROLE_ONLY: its three rows are equal).
+
+--regions compiles with -gline-tables-only as well and attributes every instruction of the two role builds to source
+regions, twice: by the phase of the engine body it was inlined into (the outermost frame of its location: the body's
+marker comments and a few anchor lines split it), and by the function its own line lies in (the innermost frame: the
+inlined helpers).  Same columns per region; regions without instructions are left out.
 """
 import argparse
 import concurrent.futures as cf
@@ -27,7 +32,8 @@ def makefile_flags(pkg):
     """HIPCC, HIPFLAGS and ENGINEFLAGS as the Makefile sets them."""
     text = open(os.path.join(pkg, "Makefile")).read()
     var = {}
-    for m in re.finditer(r"^(\w+)\s*[?:]?=\s*(.*)$", text, re.M):
+    # (plain and target-specific assignments: "build/x.o build/y.o: ENGINEFLAGS := ...")
+    for m in re.finditer(r"^(?:[^\n#=:]+:[ \t]*)?(\w+)[ \t]*[?:]?=[ \t]*(.*)$", text, re.M):
         var.setdefault(m.group(1), m.group(2).strip())
     def expand(s):
         for _ in range(4):
@@ -37,11 +43,96 @@ def makefile_flags(pkg):
     return hipcc, expand(var["HIPFLAGS"]).split() + expand(var.get("ENGINEFLAGS", "")).split()
 
 
+# lines of owgs_engine_body that start a region besides its marker comments (// ==== title, // ---- title)
+BODY_ANCHORS = [
+    (r"^\s+if \(sempty\) \{", "lanes' walks: start and choice"),
+    (r"if \(maxc == 1 && pool_mode == 0\) \{", "lanes' walks: plain 4-step groups"),
+    (r"if \(maxc > 1 && pool_mode == 0\) \{", "lanes' walks: concurrent 4-step groups"),
+    (r"for \(int k = 0; k < KPROBE_G; \+\+k\) \{", "lanes' walks: general walk"),
+    (r"if \(!done\) done = mm >", "re-decisions: walk"),
+    (r"if \(!done\) break;  // a long walk", "re-decisions: after the walk"),
+    (r"if \(act && li >= l0 && li < l\) \{", "commit: decisions of lanes [f, l)"),
+    (r"if \(act && li >= l\) \{", "commit: lanes from l on"),
+]
+BODY = "owgs_engine_body"
+
+
+def source_regions(path):
+    """(functions, phases) of one source file: functions = [(first line, last line, name)] of the definitions that
+    start in column 0; phases = [(first line, title)] inside owgs_engine_body, in source order."""
+    funcs, phases, cur = [], [], None
+    for no, line in enumerate(open(path, errors="replace").read().splitlines(), 1):
+        if cur is None:
+            sig = re.sub(r"__launch_bounds__\([^)]*\)", "", line)
+            m = re.match(r"^[A-Za-z_][^;#]*?\b(\w+)\s*\(", sig)
+            if m and not re.match(r"^(typedef|struct|namespace|extern|static_assert|using|template|return|if|for|while)\b", line):
+                if re.search(r"\{.*\}\s*(//.*)?$", line):
+                    funcs.append((no, no, m.group(1)))  # a one-line definition
+                elif not line.rstrip().endswith(";"):
+                    cur = (no, m.group(1))
+            continue
+        if line.startswith("}"):
+            funcs.append((cur[0], no, cur[1]))
+            cur = None
+            continue
+        if cur[1] != BODY:
+            continue
+        m = re.match(r"^\s+// (?:={8,}|-{4,}) (.+)$", line)
+        if m:
+            phases.append((no, m.group(1).strip()[:56]))
+            continue
+        for pat, title in BODY_ANCHORS:
+            if re.search(pat, line):
+                phases.append((no, title))
+    return funcs, phases
+
+
+class Regions:
+    def __init__(self, pkg):
+        self.pkg, self.files = pkg, {}
+
+    def _file(self, path):
+        if path not in self.files:
+            full = path if os.path.isabs(path) else os.path.join(self.pkg, path)
+            self.files[path] = source_regions(full) if os.path.exists(full) and "/csrc/" in "/" + path else None
+        return self.files[path]
+
+    def func(self, path, line):
+        f = self._file(path)
+        if f is None:
+            return "(runtime headers)"
+        if line == 0:
+            return "(compiler-generated)"
+        for a, b, name in f[0]:
+            if a <= line <= b:
+                return name
+        return os.path.basename(path)
+
+    def phase(self, frames):
+        """frames: innermost first.  The outermost frame inside owgs_engine_body names the phase; code outside the
+        body goes by its outermost function (the kernel)."""
+        path, line = frames[-1]
+        for fr in reversed(frames):
+            if self.func(*fr) == BODY:
+                path, line = fr
+                break
+        name = self.func(path, line)
+        if name != BODY:
+            return name
+        cur = "prologue"
+        for no, title in self._file(path)[1]:
+            if no > line:
+                break
+            cur = title
+        return "body: " + cur
+
+
 def compile_asm(pkg, src, extra, out):
     hipcc, flags = makefile_flags(pkg)
+    # (run inside the package, so that the locations --regions reads name its files as csrc/NAME)
     cmd = [hipcc] + flags + extra + ["--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage", "-o", out,
-                                     os.path.join(pkg, "csrc", src)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
+                                     os.path.join("csrc", src)]
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=pkg)
     if r.returncode != 0:
         sys.stderr.write(r.stderr)
         raise SystemExit(f"{src}: compile failed")
@@ -53,6 +144,56 @@ def short_name(mangled):
     if not m:
         return None
     return f"{m.group(1)}<{m.group(2)}>" + (" narrow" if "owgs_narrow" in mangled else "")
+
+
+def new_counts():
+    return dict(total=0, s=0, v=0, ds=0, mem=0, other=0, readlane=0, writelane=0)
+
+
+def count_op(c, op):
+    c["total"] += 1
+    if op.startswith(MEM_PREFIXES):
+        c["mem"] += 1
+    elif op.startswith("s_"):
+        c["s"] += 1
+    elif op.startswith("v_"):
+        c["v"] += 1
+        c["readlane"] += op.startswith("v_readlane")
+        c["writelane"] += op.startswith("v_writelane")
+    elif op.startswith("ds_"):
+        c["ds"] += 1
+    else:
+        c["other"] += 1
+
+
+def parse_regions(text, reg):
+    """{kernel: (by phase, by function)}: each instruction goes to the location of the last .loc before it, whose
+    comment lists the inlining chain, innermost frame first: file:line:col @[ file:line:col @[ .. ] ]."""
+    out, cur, loc, ph = {}, None, None, ""
+    for line in text.splitlines():
+        if cur is None:
+            m = re.match(r"^(_Z\w+):", line)
+            if m and short_name(m.group(1)):
+                cur, loc, ph = short_name(m.group(1)), None, "(no location)"
+                out[cur] = ({}, {})
+            continue
+        if line.startswith(".Lfunc_end"):
+            cur = None
+            continue
+        if re.match(r"^\s+\.loc\s", line):
+            frames = re.findall(r"([^\s\[\]]+):(\d+):\d+", line.split(";", 1)[1]) if ";" in line else []
+            loc = [(f, int(n)) for f, n in frames] or None
+            continue
+        m = re.match(r"^\s+([a-z][a-z0-9_]+)(\s|$)", line)
+        if not m:
+            continue
+        fn = reg.func(*loc[0]) if loc else "(no location)"
+        # code without a line (spill code, merged instructions) goes with the phase of the located code before it
+        if loc and loc[-1][1] != 0:
+            ph = reg.phase(loc)
+        count_op(out[cur][0].setdefault(ph, new_counts()), m.group(1))
+        count_op(out[cur][1].setdefault(fn, new_counts()), m.group(1))
+    return out
 
 
 def parse_asm(text):
@@ -109,24 +250,30 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--src", default=os.path.join(HERE, "..", "openwhisk_amd"), help="the openwhisk_amd/ directory to read")
     ap.add_argument("--only-kernel", default="owgs_engine_kernel", help="substring of the kernels to print ('' = all three)")
+    ap.add_argument("--regions", action="store_true", help="attribute the role builds' instructions to source regions")
     a = ap.parse_args()
     pkg = os.path.abspath(a.src)
     builds = [("both roles", []), ("engine waves", ["-DOWGS_ROLE_ONLY=0"]), ("I/O wave", ["-DOWGS_ROLE_ONLY=1"])]
     srcs = ["owgs_kernels.hip", "owgs_engine_narrow.hip"]
-    res = {}
+    extra_of = dict(builds)
+    res, regs = {}, {}
+    dbg = ["-gline-tables-only"] if a.regions else []
     with tempfile.TemporaryDirectory() as d, cf.ThreadPoolExecutor(max_workers=6) as ex:
         futs = {}
         for bi, (bname, extra) in enumerate(builds):
             for src in srcs:
-                futs[ex.submit(compile_asm, pkg, src, extra, os.path.join(d, f"{bi}_{src}.s"))] = (bname, src)
+                futs[ex.submit(compile_asm, pkg, src, extra + dbg, os.path.join(d, f"{bi}_{src}.s"))] = (bname, src)
         for f, (bname, src) in futs.items():
             asm, rem = f.result()
             counts, remarks = parse_asm(asm), parse_remarks(rem)
+            if a.regions and extra_of[bname]:
+                for k, r in parse_regions(asm, Regions(pkg)).items():
+                    regs[(k, bname)] = r
             for k, c in counts.items():
                 c.update(remarks.get(k, {}))
                 res[(k, bname)] = c
     _, flags = makefile_flags(pkg)
-    print("# flags: " + " ".join(flags))
+    print("# flags: " + " ".join(flags + dbg))
     cols = ["total", "s", "v", "ds", "mem", "other", "readlane", "writelane", "sgpr", "sgpr_spill", "vgpr", "vgpr_spill",
             "scratch"]
     print(f"{'kernel':42s} {'build':13s} " + " ".join(f"{c:>10s}" for c in cols))
@@ -136,6 +283,15 @@ def main():
         for bname, _ in builds:
             c = res[(k, bname)]
             print(f"{k:42s} {bname:13s} " + " ".join(f"{c.get(x, -1):>10d}" for x in cols))
+    rcols = cols[:8]
+    for (k, bname) in sorted(regs):
+        if a.only_kernel not in k:
+            continue
+        for what, table in zip(("phase (outermost frame)", "function (innermost frame)"), regs[(k, bname)]):
+            print(f"\n# {k}, {bname}: instructions by {what}")
+            print(f"{'region':64s} " + " ".join(f"{c:>10s}" for c in rcols))
+            for name, c in table.items():  # (first appearance in the code: roughly source order)
+                print(f"{name:64s} " + " ".join(f"{c[x]:>10d}" for x in rcols))
 
 
 if __name__ == "__main__":
