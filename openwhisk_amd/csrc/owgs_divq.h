@@ -36,7 +36,7 @@
 
 #define OWGS_DIVQ_XMAX (1 << 22)  // the capacity quotient is exact for operands below this
 #define OWGS_DIVQ_MEM_ANY 4095    // ... and the capacity clamped to 1024 for any operand up to this divisor
-#define OWGS_DIVQ_CAPMAX 1024     // the engine's capacity clamp (CAPMAX; checked where the engine defines it)
+#define OWGS_DIVQ_CAPMAX 1024     // the engine's capacity clamp (OWGS_CAPMAX; checked where the engine defines it)
 #define OWGS_DIVQ_MAX_MEM 131071  // the largest memory limit (OWGS_MAX_MEM_MB; checked there too)
 
 // the reciprocal of the capacity form (once per divisor); mem >= 1

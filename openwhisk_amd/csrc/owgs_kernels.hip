@@ -34,6 +34,7 @@
 
 #include <atomic>
 
+#include "owgs_device.h"
 #include "owgs_divq.h"
 #include "owgs_internal.h"
 #include "owgs_launch.h"
@@ -51,8 +52,6 @@ namespace OWGS_VARIANT_NS {
 #define OWGS_GEOM(name) name
 #endif
 
-typedef unsigned long long u64;
-
 #define K_NONE 0
 #define K_THROW 1
 #define K_TARGET 2
@@ -69,29 +68,8 @@ typedef unsigned long long u64;
 #ifndef OWGS_OVF
 #define OWGS_OVF 1  // 0: measurement variant without the overflow table's fall-through paths
 #endif
-#ifndef OWGS_HOT_ROT
-#define OWGS_HOT_ROT 0  // engine wave (w + OWGS_HOT_ROT) % OWGS_EW walks hot slots w + 1, w + 1 + 8, .. (load balance)
-#endif
-#ifndef OWGS_HOT_IO
-#define OWGS_HOT_IO 1  // the I/O wave takes a share of the hot-action walks
-#endif
-#ifndef OWGS_QUEUE_IO
-#define OWGS_QUEUE_IO 1  // ... and pops queued long walks when the queue is shared
-#endif
 #ifndef OWGS_CSCAN_MIN_N
 #define OWGS_CSCAN_MIN_N (OWGS_CTC / 2)  // pools at most this large walk instead of scanning the table
-#endif
-#ifndef OWGS_EXT
-#define OWGS_EXT 1  // stopping maxConcurrent == 1 lanes are re-decided exactly inside the pass (see the commit phase)
-#endif
-#ifndef OWGS_COOP_GIVEBACK
-#define OWGS_COOP_GIVEBACK 1  // before the re-decisions the engine lanes give their own takes back (0: the I/O wave, from fxa)
-#endif
-#ifndef OWGS_COOP_CLASH
-#define OWGS_COOP_CLASH 1  // after the re-decisions the lanes that stay test themselves against the re-decided sets (0: the I/O wave marks them in fxa)
-#endif
-#ifndef OWGS_DIVQ
-#define OWGS_DIVQ 1  // walk arithmetic by the exact forms of owgs_divq.h (0: float reciprocal plus correction chains)
 #endif
 #ifndef EXT_MAX
 #define EXT_MAX 48  // re-decisions per pass
@@ -99,14 +77,6 @@ typedef unsigned long long u64;
 #ifndef EXT_ROUNDS
 #define EXT_ROUNDS 8  // walk rounds (128 steps each) a re-decision may take; a longer walk waits for the next pass
 #endif
-#ifndef OWGS_PRE
-#define OWGS_PRE 0  // stopping lanes walk their own re-decision in validate, in parallel (see the commit phase)
-#endif
-#ifndef PRE_G
-#define PRE_G 6  // 4-step groups such a walk may take (beyond them the I/O wave walks it)
-#endif
-// the pre-walk's record of the invokers it skipped: one bit of a 64-bit signature per invoker
-__device__ __forceinline__ uint32_t pre_bit(int x) { return ((uint32_t)x * 0x9E3779B1u) >> 26; }
 // fxa[li] (per lane of the pass, stream order): x = action | not known to fit << 24 | exempt << 25 | re-decidable << 26
 // | re-decided << 27 | kind << 28 | clash << 30; y = target (0xFFFF none) | walk step << 16 (after a re-decision: the
 // new ones); z = the action's meta.x (home | step << 15 | pool); w = mem | took memory << 31
@@ -116,9 +86,6 @@ __device__ __forceinline__ uint32_t pre_bit(int x) { return ((uint32_t)x * 0x9E3
 #define FX_OK (1u << 26)
 #define FX_DONE (1u << 27)
 #define FX_CLASH (1u << 30)  // a lane after the pass limit that targets a re-decided lane's invoker or shares its action
-#ifndef OWGS_CSCAN_ON
-#define OWGS_CSCAN_ON 1
-#endif
 
 #ifndef KPROBE
 #define KPROBE 16  // walk steps a maxConcurrent==1 lane probes on its own before the wave-cooperative walk (x4)
@@ -129,7 +96,6 @@ __device__ __forceinline__ uint32_t pre_bit(int x) { return ((uint32_t)x * 0x9E3
 #ifndef FGRP
 #define FGRP 4  // walk steps per group of the maxConcurrent == 1 fast path (their reads issue together)
 #endif
-#define CAPMAX 1024  // capacities are clamped: a lane's rank is < OWGS_WL
 #ifndef LW_Q
 #define LW_Q 2  // walk steps each lane probes per round of a wave-cooperative long walk (2 vs 4: 35.4 vs 36.1 ms
                 // headline, 130 vs 137 ms configs[1], 222 vs 229 ms C5 shard 0 of 8; round 2)
@@ -178,7 +144,7 @@ __device__ __forceinline__ unsigned long long memtime_pinned() {
 #define SC_CLAST 12  // primary entries (live) right after the last table rebuild
 #define SC_LQN 10   // long walks queued in this pass
 #define SC_LQH 11   // next queued long walk to take
-#define SC_LFIN 14  // pass limit after the in-pass re-decisions (OWGS_EXT)
+#define SC_LFIN 14  // pass limit after the in-pass re-decisions
 #define SC_NEXT 15  // re-decisions in this pass
 // [2][CFT_N] per pass parity and hashed fqn@version key: the first lane of the pass with a concurrent forced acquire
 // of that key (its new container's free slots can only change the walks of lanes with the same key, NS:57-82)
@@ -219,60 +185,6 @@ __host__ __device__ inline int wave_off(int len, int w) {
 }
 
 // ------------------------------------------------------------------------------------------------ helpers
-__device__ __forceinline__ u64 splitmix64(u64 x) {
-    x += 0x9E3779B97F4A7C15ULL;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
-    return x ^ (x >> 31);
-}
-
-// Counter RNG replacing ThreadLocalRandom.nextInt(|H|) (SCPB:421); identical to oracle/owsched_oracle.c
-__device__ __forceinline__ uint32_t rng_index(u64 seed, u64 seq, uint32_t n) {
-    u64 u = splitmix64(seed ^ (seq * 0x9E3779B97F4A7C15ULL)) >> 32;
-    return (uint32_t)((u * (u64)n) >> 32);
-}
-
-__device__ __forceinline__ int ffs64(u64 m) { return __ffsll((long long)m) - 1; }
-
-// DPP (GFX9 row_shr / row_bcast) wave64 scans: no LDS round trip
-template <int CTRL, int ROWM>
-__device__ __forceinline__ int dpp_add_src(int v) {
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, ROWM, 0xf, true);  // out-of-row / masked lanes read 0
-}
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    v += dpp_add_src<0x111, 0xf>(v);  // row_shr:1
-    v += dpp_add_src<0x112, 0xf>(v);  // row_shr:2
-    v += dpp_add_src<0x114, 0xf>(v);  // row_shr:4
-    v += dpp_add_src<0x118, 0xf>(v);  // row_shr:8
-    v += dpp_add_src<0x142, 0xa>(v);  // row_bcast:15 -> rows 1, 3
-    v += dpp_add_src<0x143, 0xc>(v);  // row_bcast:31 -> rows 2, 3
-    return v;
-}
-template <int CTRL, int ROWM>
-__device__ __forceinline__ int dpp_keep(int old, int v) {
-    return __builtin_amdgcn_update_dpp(old, v, CTRL, ROWM, 0xf, false);  // invalid source lanes keep `old`
-}
-__device__ __forceinline__ int wave_incl_max(int v) {
-    const int I = (int)0x80000000;
-    v = max(v, dpp_keep<0x111, 0xf>(I, v));
-    v = max(v, dpp_keep<0x112, 0xf>(I, v));
-    v = max(v, dpp_keep<0x114, 0xf>(I, v));
-    v = max(v, dpp_keep<0x118, 0xf>(I, v));
-    v = max(v, dpp_keep<0x142, 0xa>(I, v));
-    v = max(v, dpp_keep<0x143, 0xc>(I, v));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-    const int I = (int)0x80000000;
-    v = max(v, dpp_keep<0x111, 0xf>(I, v));
-    v = max(v, dpp_keep<0x112, 0xf>(I, v));
-    v = max(v, dpp_keep<0x114, 0xf>(I, v));
-    v = max(v, dpp_keep<0x118, 0xf>(I, v));
-    v = max(v, dpp_keep<0x142, 0xa>(I, v));
-    v = max(v, dpp_keep<0x143, 0xc>(I, v));
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
 // interleaved {key, value} table (engine LDS).  One aligned block of 4 entries: 1 = key found (*val, *idx),
 // 0 = an empty entry ends the chain, 2 = the chain continues in the next block.
 __device__ __forceinline__ int ct_block(uint4 e01, uint4 e23, uint32_t key, uint32_t h, uint32_t* val, int* idx) {
@@ -379,95 +291,6 @@ __device__ __forceinline__ int ct_resolve2(const uint2* ct, const OwgsOvf& O, bo
     return ci;
 }
 
-// min(floor(pv / m), CAPMAX) for pv >= 0, 0 when pv < m; float reciprocal + one correction (pv / m < 2^10)
-__device__ __forceinline__ int cap_of(int pv, int m, float rm) {
-    if (pv < m) return 0;
-    if (pv >= m * CAPMAX) return CAPMAX;
-    int q = (int)((float)pv * rm);
-    const int r = pv - q * m;
-    if (r < 0) --q;
-    else if (r >= m) ++q;
-    return q;
-}
-
-// x mod n for 0 <= x < 2^31, 1 <= n < 2^15 without an integer division: float reciprocal, then exact correction
-__device__ __forceinline__ int mod_fast(int x, int n, float rn) {
-    const int q = (int)((float)x * rn);  // |q - x / n| <= 2 for x < 2^31, n < 2^15
-    int r = x - q * n;
-    r += r < 0 ? n : 0;
-    r += r < 0 ? n : 0;
-    r -= r >= n ? n : 0;
-    r -= r >= n ? n : 0;
-    return r;
-}
-
-// branch-free cap_of (float reciprocal + one correction); pv may be negative (forced acquires)
-__device__ __forceinline__ int cap_bf(int pv, int m, float rm) {
-    int q = (int)((float)max(pv, 0) * rm);
-    const int r = pv - q * m;
-    q += r >= m ? 1 : 0;
-    q -= r < 0 ? 1 : 0;
-    q = min(q, CAPMAX);
-    return pv >= m ? q : 0;
-}
-
-// The walk arithmetic of the chunked engine.  OWGS_DIVQ = 1: the exact forms of owgs_divq.h, whose
-// per-divisor constants are computed where the divisor is fixed (the lane decode, the kernel prologue); 0: the forms
-// above, which need none.  DivCap: capacities by one memory limit; DivPos: positions in one pool.
-struct DivCap {
-    int m;
-    float rm, hrm;
-};
-struct DivPos {
-    int n;
-    uint32_t M;
-};
-__device__ __forceinline__ DivCap div_cap_of(int m, float rm) { return DivCap{m, rm, 0.5f * rm}; }
-// the reciprocal a DivCap needs: correctly rounded (OWGS_DIVQ), or the hardware's estimate
-__device__ __forceinline__ float div_rm(int m) {
-#if OWGS_DIVQ
-    return owgs_divq_rm(m);
-#else
-    return __builtin_amdgcn_rcpf((float)m);
-#endif
-}
-__device__ __forceinline__ DivCap div_cap(int m) { return div_cap_of(m, div_rm(m)); }
-// min(floor(pv / m), CAPMAX), 0 for pv < m (negative permits included); usable permits are below 2^22
-__device__ __forceinline__ int cap_q(int pv, const DivCap& d) {
-#if OWGS_DIVQ
-    return owgs_divq_cap(pv, d.rm, d.hrm, CAPMAX);
-#else
-    return cap_bf(pv, d.m, d.rm);
-#endif
-}
-// the general walk's capacity (pv < OWGS_PLIM): the same value; the old form branches
-__device__ __forceinline__ int cap_g(int pv, const DivCap& d) {
-#if OWGS_DIVQ
-    return cap_q(pv, d);
-#else
-    return cap_of(pv, d.m, d.rm);
-#endif
-}
-__device__ __forceinline__ DivPos div_pos(int n, uint32_t M) { return DivPos{n, M}; }
-// x mod n for 0 <= x < 2^31, 1 <= n < 2^15
-__device__ __forceinline__ int pos_mod(int x, const DivPos& d) {
-#if OWGS_DIVQ
-    return owgs_divq_mod(x, d.n, d.M);
-#else
-    return mod_fast(x, d.n, __builtin_amdgcn_rcpf((float)d.n));
-#endif
-}
-// x mod n for ranks (< 2^10) against maxConcurrent (< 2^12): owgs_divq.h's small remainder takes the hardware's
-// reciprocal estimate, so no division per lane
-static_assert(CAPMAX == OWGS_DIVQ_CAPMAX && OWGS_MAX_MEM_MB == OWGS_DIVQ_MAX_MEM, "owgs_divq.h mirrors the engine's bounds");
-__device__ __forceinline__ int small_mod(int x, int n) {
-#if OWGS_DIVQ
-    return owgs_divq_small_mod(x, n, __builtin_amdgcn_rcpf((float)n));
-#else
-    return mod_fast(x, n, __builtin_amdgcn_rcpf((float)n));
-#endif
-}
-
 // LDS-DMA (global_load_lds): each lane's 16 (4) bytes land at lds_dst + 16 (4) * lane.  M0 is compiler-reserved:
 // saved and restored inside the statement (cdna_hip_programming.md section 5.7).  The issuing wave must wait
 // vmcnt before a barrier that publishes the bytes.
@@ -519,7 +342,7 @@ constexpr uint32_t LY_SPC = LY_NEXTL + 4u * OWGS_WL;                 // memory e
 constexpr uint32_t LY_CDIRTY = LY_SPC + 4u * OWGS_WL;                // [2][OWGS_WL] bytes, pass parity x first lane of an action: re-speculated
 constexpr uint32_t LY_SKEY = LY_CDIRTY + 2u * OWGS_WL;               // per lane {slot key, action} (shared-key check)
 constexpr uint32_t LY_LQ = LY_SKEY + 8u * OWGS_WL;                   // long-walk queue: {record | rank, step, position, cum} / result
-constexpr uint32_t LY_FXA = LY_LQ + 16u * OWGS_WL;                   // per lane: validation summary / in-pass re-decision (OWGS_EXT)
+constexpr uint32_t LY_FXA = LY_LQ + 16u * OWGS_WL;                   // per lane: validation summary / in-pass re-decision
 constexpr uint32_t LY_UNI_BYTES = LY_FXA + 16u * OWGS_WL - LY_UNI;
 constexpr uint32_t LY_RC = LY_UNI;                                   // release phase: one counter per concurrency-table entry
 constexpr uint32_t LY_STGX = LY_UNI + LY_UNI_BYTES;                  // release slots of 3 chunks (g, g+1 staged, g+2 streaming in)
@@ -1126,20 +949,6 @@ __device__ __forceinline__ int usable_before(const EngineCtx& E, int x) {
     return (int)E.pc[w] + __popc(m);
 }
 
-// position of the need-th set bit (0-based) of m, need < popc(m): halving by popcounts, no loop over the bits
-__device__ __forceinline__ int select_in_word(uint32_t m, int need) {
-    int pos = 0;
-#pragma unroll
-    for (int w = 16; w >= 1; w >>= 1) {
-        const int c = __popc(m & ((1u << w) - 1u));
-        const bool up = need >= c;
-        need -= up ? c : 0;
-        m = up ? m >> w : m;
-        pos += up ? w : 0;
-    }
-    return pos;
-}
-
 // k-th usable id (0-based) at or after id lo (identity pools): binary search over the word prefix counts
 __device__ __forceinline__ int select_usable(const EngineCtx& E, int lo, int k) {
     const int target = usable_before(E, lo) + k;  // global rank of the wanted id
@@ -1270,11 +1079,9 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
     // positions in the two pools: their multipliers, once per launch (nobody walks an empty pool).  They live in
     // vector registers, of which the kernel has some to spare: as scalars they would be two more values spilled to
     // VGPR lanes and read back at every use
-    uint32_t mgm = OWGS_DIVQ ? owgs_divq_magic((uint32_t)max(nm, 1)) : 0u;
-    uint32_t mgb = OWGS_DIVQ ? owgs_divq_magic((uint32_t)max(nb, 1)) : 0u;
-#if OWGS_DIVQ
+    uint32_t mgm = owgs_divq_magic((uint32_t)max(nm, 1));
+    uint32_t mgb = owgs_divq_magic((uint32_t)max(nb, 1));
     asm volatile("" : "+v"(mgm), "+v"(mgb));
-#endif
     const DivPos dvm = div_pos(nm, mgm), dvb = div_pos(nb, mgb);
     const int words = (A.n_ids + 31) >> 5;
 
@@ -1287,7 +1094,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
     // the capacity form's domain (owgs_divq.h): permits below 2^22 MB, or memory limits of at most
     // OWGS_DIVQ_MEM_ANY MB (every larger quotient is clamped).  The host keeps states with both off this engine; one
     // that arrives all the same is refused before anything is touched (OWGS_ERR_PERMITS)
-    const bool wide_mem = OWGS_DIVQ && (A.opts & OWGS_OPT_WIDE_MEM) != 0;  // (uniform)
+    const bool wide_mem = (A.opts & OWGS_OPT_WIDE_MEM) != 0;  // (uniform)
     if (A.rel_bound || wide_mem) lds_sync();  // (SC_RRISK is set below)
     bool rrisk = false;    // (owgs_process_batch) a slot the call's releases could push out of the LDS range
     // permits four slots per 16-byte load, with their usable word and (owgs_process_batch) their release bounds, all
@@ -1400,7 +1207,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
     E.nb = nb;
 
     uint32_t st_pass = 0, st_probe = 0, st_fb = 0, st_long = 0, st_chunk = 0, st_stop = 0, st_gprobe = 0, st_glane = 0;
-    uint32_t st_ext = 0, st_pre = 0;  // in-pass re-decisions (I/O wave), of them from the lane's own pre-walk
+    uint32_t st_ext = 0;  // in-pass re-decisions (I/O wave)
 #ifdef OWGS_EXT_PROF
     u64 xp_cyc = 0, xp_rounds = 0, xp_scans = 0, xp_ph[4] = {0, 0, 0, 0};
 #endif
@@ -1791,7 +1598,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                 const int v = P[i];
                 const bool unusable = pool_mode == 0 && i < A.n_ids && !((ub[i >> 5] >> (i & 31)) & 1u);
                 const int pvv = unusable ? v - OWGS_PENC : v;
-                if (pvv >= OWGS_PLIM || (OWGS_DIVQ && (A.opts & OWGS_OPT_WIDE_MEM) && pvv >= OWGS_DIVQ_XMAX))
+                if (pvv >= OWGS_PLIM || ((A.opts & OWGS_OPT_WIDE_MEM) && pvv >= OWGS_DIVQ_XMAX))
                     err |= OWGS_ERR_PERMITS;
             }
             int m0 = (int)0x80000000, m1 = (int)0x80000000;
@@ -1973,9 +1780,10 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                 // slot h goes to the I/O wave when h % (OWGS_EW + 1) == 0 (it holds no lanes: its speculation is
                 // otherwise idle), else to engine wave h % (OWGS_EW + 1) - 1
                 {
-                    const int wr = (wave + OWGS_EW - OWGS_HOT_ROT % OWGS_EW) % OWGS_EW;  // (io: unused)
-                    const int hw = OWGS_HOT_IO ? (io ? 0 : wr + 1) : (io ? NHOT : wr);
-                    for (int h = hw; h < nhot; h += OWGS_HOT_IO ? OWGS_EW + 1 : OWGS_EW) {
+                    // (wr == wave for every engine wave; the compiler cannot know wave < OWGS_EW, so the plain `wave`
+                    // would change the generated code: left for the change that is measured on a device)
+                    const int wr = (wave + OWGS_EW) % OWGS_EW;  // (io: unused)
+                    for (int h = io ? 0 : wr + 1; h < nhot; h += OWGS_EW + 1) {
                         const uint4 d = hdir[h];
                         if (d.z & (OWGS_AM_THROW | OWGS_AM_EMPTY)) continue;
                         if (hflag[h] != f) continue;  // no lane of this action speculates in this pass
@@ -2028,7 +1836,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                     } else {
                                         uint32_t v;
                                         ct_find2(ct, A.ovf, ovf_on, ct_key(id, hslot), &v);
-                                        cap = (int)(v & OWGS_CT_C_MASK) + min(cap_q(pv, dch) * hmc, CAPMAX);
+                                        cap = (int)(v & OWGS_CT_C_MASK) + min(cap_q(pv, dch) * hmc, OWGS_CAPMAX);
                                     }
                                 }
                             }
@@ -2086,7 +1894,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                             kind = K_HOT;
                         } else if (maxc == 1 && mem > U && ((A.shortcut_ok >> pool) & 1)) {
                             kind = K_FALLBACK;  // every usable permit < mem: the walk fails everywhere
-                        } else if (OWGS_CSCAN_ON && maxc > 1 && mem > U && pool_mode == 0 && n > OWGS_CSCAN_MIN_N && !ovf_on) {
+                        } else if (maxc > 1 && mem > U && pool_mode == 0 && n > OWGS_CSCAN_MIN_N && !ovf_on) {
                             kind = K_CSCAN;  // no invoker can open a container: capacity = the key's open ones
                             ws = s;          // (the ordinary walk's start, should the key have > 64 of them)
                             wpos = pos_mod(home + s * step, dvn);
@@ -2204,7 +2012,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
 #endif
                                         }
                                         const int cap = pv[k] < OWGS_PLIM
-                                                            ? (int)(v & OWGS_CT_C_MASK) + min(cap_q(pv[k], dcm) * maxc, CAPMAX)
+                                                            ? (int)(v & OWGS_CT_C_MASK) + min(cap_q(pv[k], dcm) * maxc, OWGS_CAPMAX)
                                                             : 0;
                                         const bool h = open && !fin && kc + cap > r;
                                         ended = ended || fin;
@@ -2253,11 +2061,11 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                 if (id >= 0) {
                                     int cap;
                                     if (maxc == 1) {
-                                        cap = cap_g(pv, dcm);
+                                        cap = cap_q(pv, dcm);
                                     } else {
                                         uint32_t v;
                                         const int ci = ct_find2(ct, A.ovf, ovf_on, ct_key(id, slot), &v);
-                                        cap = (int)(v & OWGS_CT_C_MASK) + min(cap_g(pv, dcm) * maxc, CAPMAX);
+                                        cap = (int)(v & OWGS_CT_C_MASK) + min(cap_q(pv, dcm) * maxc, OWGS_CAPMAX);
                                         if (cum + cap > r) {
                                             cval = v;
                                             cidx = ci;
@@ -2444,7 +2252,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
 #ifdef OWGS_PROFILE
                 const u64 ts_b8b = memtime_pinned();
 #endif
-                if (!io || (OWGS_QUEUE_IO && lqs)) {  // (the I/O wave takes shared-queue walks too: it holds no lanes)
+                if (!io || lqs) {  // (the I/O wave takes shared-queue walks too: it holds no lanes)
                     const int nq = lqs ? sc[SC_LQN] : wave * OWGS_LPW + nown;
                     int own = wave * OWGS_LPW;
                     for (;;) {
@@ -2560,7 +2368,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                     const int bst = ct_block(ea[q], eb[q], key, hx[q], &v, &ci);
                                     if (bst == 2 || (bst == 0 && ovf_on))
                                         ci = ct_resolve2(ct, A.ovf, ovf_on, bst, key, hx[q], &v, ci);
-                                    cap = (int)(v & OWGS_CT_C_MASK) + min(cap_q(pv[q], dcj) * cj, CAPMAX);
+                                    cap = (int)(v & OWGS_CT_C_MASK) + min(cap_q(pv[q], dcj) * cj, OWGS_CAPMAX);
                                 }
                                 const int inc = wave_incl_scan(cap);
                                 const u64 hm = __ballot(in && (bad || cum + inc > rj));
@@ -2790,7 +2598,6 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                     }
 #endif
                 }
-#if OWGS_EXT
                 if (act) {  // the summary the in-pass re-decisions read (commit phase)
                     const bool exempt = !part || kind == K_FALLBACK;
                     const bool rd = maxc == 1 && pool_mode == 0 && kind == K_TARGET && a != (int)OWGS_REC_NOACT;
@@ -2798,63 +2605,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                              (rd ? FX_OK : 0u),
                                          (part ? (uint32_t)t : FX_NOT) | ((uint32_t)s_t << 16), rc4.x,
                                          (uint32_t)mem | ((part && cons) ? 0x80000000u : 0u));
-#if OWGS_PRE
-                    // pre-walk: a lane that does not fit walks on from its speculated step now, on the permits every
-                    // earlier lane of the pass leaves where it speculated: the tentative permits (all lanes' takes)
-                    // plus the takes of this lane and the later ones at each probed invoker (bucket lists).  That is
-                    // this lane's exact decision unless an earlier lane is re-decided first; the I/O wave checks that
-                    // (commit phase) with the signature of the invokers skipped here.  Result -> lq[li] (free after
-                    // the speculation), invalid unless a target was found within PRE_G groups.
-                    uint4 pre = make_uint4(0u, 0u, 0u, 0u);
-                    if (nf && rd) {
-                        const int base = pool ? A.n_ids - nb : 0;
-                        uint32_t blo = 0u, bhi = 0u;
-                        auto bmark = [&](int x) {
-                            const uint32_t h = pre_bit(x);
-                            if (h < 32u) blo |= 1u << h;
-                            else bhi |= 1u << (h - 32u);
-                        };
-                        bmark(t);  // (a lane re-decided away from t leaves room there)
-                        int s = s_t + 1;
-                        int pos = pos_mod(home + s * step, dvn);
-                        bool found = false;
-                        int tp = 0, sp = 0;
-#pragma unroll 1
-                        for (int g4 = 0; g4 < PRE_G && !found && s < n; ++g4) {
-                            int ps[4], pv[4];
-                            uint32_t bh[4];
-                            int pp = pos;
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                ps[k] = base + pp;
-                                pv[k] = P[ps[k]];
-                                bh[k] = bhead[((uint32_t)ps[k] * 2654435761u) >> (32 - OWGS_NBK_LOG2)];
-                                pp += step;
-                                pp -= pp >= n ? n : 0;
-                            }
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                if (found || s + k >= n || pv[k] >= OWGS_PLIM) continue;  // (unusable: stays so)
-                                int room = pv[k];
-                                for (int m = (int)bh[k] - 1; m >= 0; m = nextl[m] - 1)
-                                    if (m > li && spt[m] == ps[k]) room += spc[m];  // later lanes' takes back
-                                if (room >= mem) {
-                                    found = true;
-                                    tp = ps[k];
-                                    sp = s + k;
-                                } else {
-                                    bmark(ps[k]);
-                                }
-                            }
-                            s += 4;
-                            pos = pp;
-                        }
-                        if (found) pre = make_uint4(0x80000000u | (uint32_t)tp, (uint32_t)sp, blo, bhi);
-                    }
-                    lq[li] = pre;
-#endif
                 }
-#endif
                 if (!io) {
                     // (the lanes of a wave are not in stream order) the wave's smallest such lane
                     if (__ballot(nf)) {
@@ -2874,7 +2625,6 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                     l = f + 1;
                     err |= OWGS_ERR_INTERNAL;
                 }
-#if OWGS_EXT
                 // ---- in-pass re-decisions.  Every lane before l is exact.  Lane l (maxConcurrent == 1, identity pool,
                 // a walk target) is decided exactly here instead of in another pass: the state it sees is the
                 // frontier minus the lanes before it = the tentative permits once the lanes from l on give their takes
@@ -2890,7 +2640,6 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                 const bool fixup = l < len && (fxa[l].x & FX_OK);
                 auto hsh = [](uint32_t v) { return (v * 2654435761u) >> 21; };  // bit of a value in a 2048-bit set
                 if (fixup) {
-#if OWGS_COOP_GIVEBACK
                     // every lane from l on gives its tentative take back itself (one LDS add from its registers: what
                     // it took in the tentative phase): the permits are then exactly what lane l sees (the frontier
                     // minus the lanes before it); the lanes that commit add theirs again below.  l and fixup are
@@ -2898,22 +2647,10 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                     // every wave of both roles reaches it
                     if (!io && part && li >= l && cons) atomicAdd(&P[t], cons);
                     LDS_SYNC_T(10);
-#endif
                     if (io) {
 #ifdef OWGS_EXT_PROF
                         const u64 tx0 = memtime_pinned();
                         u64 tq_prev = tx0;
-#endif
-#if !OWGS_COOP_GIVEBACK
-                        // every lane from l on gives its tentative take back: the permits are then exactly what lane l
-                        // sees (the frontier minus the lanes before it); the lanes that commit add theirs again below
-                        for (int k0 = l; k0 < len; k0 += 64) {
-                            const int k = k0 + lane;
-                            if (k < len) {
-                                const uint4 f2 = fxa[k];
-                                if (f2.w >> 31) atomicAdd(&P[(int)(f2.y & 0xFFFFu)], (int)(f2.w & OWGS_AM_MEM_MASK));
-                            }
-                        }
 #endif
                         int L = l, nE = 0;
                         // the re-decided lanes' targets and actions as hashed 2048-bit sets over the wave's lanes
@@ -2921,13 +2658,10 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                         auto inset = [&](uint32_t bits, uint32_t h) {  // (whole wave: ds_bpermute)
                             return ((uint32_t)__shfl((int)bits, (int)(h >> 5), 64) >> (h & 31u)) & 1u;
                         };
-                        // lane i: the speculated target a re-decided lane left (room grew there), -1 = none
-                        int src = -1;
-                        (void)src;  // (read by the pre-walk check only)
                         // the pools' usable-permit bounds: only this wave changes them in this phase
                         int u0 = sc[SC_U0], u1 = sc[SC_U1];
-                        // the stop lane's summary and pre-walk, carried from the scan that found it (uniform)
-                        uint4 fx = fxa[L], px = lq[L];
+                        // the stop lane's summary, carried from the scan that found it (uniform)
+                        uint4 fx = fxa[L];
                         bool a_hit = false;  // its action was re-decided in this pass (none yet)
                         while (L < len && nE < EXT_MAX) {
                             // a re-decided action's next lane waits for the next pass (its rank, and the hot table of
@@ -2947,41 +2681,15 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                             const u64 tq0 = memtime_pinned();
                             xp_ph[0] += tq0 - tq_prev;
 #endif
-                            bool done = false;
-#if OWGS_PRE
-                            // the lane's own pre-walk (validate) assumed every earlier lane where it speculated.  Since
-                            // then the re-decided lanes moved: room grew at their old targets (none of them may be a
-                            // step the pre-walk skipped: signature test) and shrank at their new ones (the permits
-                            // here are exact for this lane: the target must still hold it)
-                            const uint32_t pxx = __builtin_amdgcn_readfirstlane(px.x);
-                            if (pxx >> 31) {
-                                const uint32_t blo = __builtin_amdgcn_readfirstlane(px.z), bhi = __builtin_amdgcn_readfirstlane(px.w);
-                                const uint32_t hb = pre_bit(src);
-                                const bool hit = src >= 0 && (((hb < 32u ? blo >> hb : bhi >> (hb - 32u)) & 1u) != 0u);
-                                if (!__ballot(hit)) {
-                                    const int tp = (int)(pxx & 0x7FFFFFFFu);
-                                    const int v = P[tp];
-                                    if (v < OWGS_PLIM && v >= mm) {
-                                        kn = K_TARGET;
-                                        tn = tp;
-                                        sn = (int)__builtin_amdgcn_readfirstlane(px.y);
-                                        done = true;
-                                        ++st_pre;
-                                    }
-                                }
-                            }
-#endif
                             // every usable permit count below mem: the walk fails (U bounds the frontier, whose
                             // permits bound this lane's)
-                            if (!done) done = mm > (pl_ ? u1 : u0) && ((A.shortcut_ok >> pl_) & 1);
+                            bool done = mm > (pl_ ? u1 : u0) && ((A.shortcut_ok >> pl_) & 1);
                             if (!done) {
                                 const DivPos dvx = pl_ ? dvb : dvm;
                                 int s0 = (int)(fy >> 16);
-#if OWGS_DIVQ
                                 // the round's first position is reduced once (one value for the wave); each lane adds
                                 // its own offset (and the second half-round's) with one conditional subtract
                                 const int loff = pos_mod(lane * st_, dvx), boff = pos_mod(64 * st_, dvx);
-#endif
                                 for (int rd = 0; rd < EXT_ROUNDS; ++rd) {
 #ifdef OWGS_EXT_PROF
                                     ++xp_rounds;
@@ -2991,16 +2699,11 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                         break;
                                     }
                                     // walk steps s0 + lane and s0 + 64 + lane ((s0 + 127) * step < 2^31)
-#if OWGS_DIVQ
                                     int pa = pos_mod(hm_ + s0 * st_, dvx) + loff;
                                     pa -= pa >= nn ? nn : 0;
                                     int pb = pa + boff;
                                     pb -= pb >= nn ? nn : 0;
                                     const int xa = base + pa, xb = base + pb;
-#else
-                                    const int xa = base + pos_mod(hm_ + (s0 + lane) * st_, dvx);
-                                    const int xb = base + pos_mod(hm_ + (s0 + 64 + lane) * st_, dvx);
-#endif
                                     const bool ia = s0 + lane < nn, ib = s0 + 64 + lane < nn;
                                     const int va = ia ? P[xa] : OWGS_PENC, vb = ib ? P[xb] : OWGS_PENC;
                                     const bool fa = va < OWGS_PLIM && va >= mm;  // (usable: flag folded in)
@@ -3044,7 +2747,6 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                 const uint32_t h1 = hsh((uint32_t)tn), h2 = hsh(fxx & OWGS_REC_NOACT);
                                 if (lane == (int)(h1 >> 5)) set_t |= 1u << (h1 & 31u);
                                 if (lane == (int)(h2 >> 5)) set_a |= 1u << (h2 & 31u);
-                                if (lane == nE) src = (int)(fy & 0xFFFFu);  // the room it left
                             }
                             ++nE;
 #ifdef OWGS_EXT_PROF
@@ -3059,11 +2761,8 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                 ++xp_scans;
 #endif
                                 const int k = k0 + lane;
-                                uint4 f2 = make_uint4(FX_EXEMPT, FX_NOT, 0u, 0u), p2 = make_uint4(0u, 0u, 0u, 0u);
-                                if (k < len) {
-                                    f2 = fxa[k];
-                                    p2 = lq[k];
-                                }
+                                uint4 f2 = make_uint4(FX_EXEMPT, FX_NOT, 0u, 0u);
+                                if (k < len) f2 = fxa[k];
                                 const uint32_t tk = f2.y & 0xFFFFu;
                                 const uint32_t ab = inset(set_a, hsh(f2.x & OWGS_REC_NOACT));
                                 const bool cl = (ab | inset(set_t, hsh(tk))) != 0u;
@@ -3076,8 +2775,6 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                     L = k0 + q;
                                     fx = make_uint4(__builtin_amdgcn_readlane(f2.x, q), __builtin_amdgcn_readlane(f2.y, q),
                                                     __builtin_amdgcn_readlane(f2.z, q), __builtin_amdgcn_readlane(f2.w, q));
-                                    px = make_uint4(__builtin_amdgcn_readlane(p2.x, q), __builtin_amdgcn_readlane(p2.y, q),
-                                                    __builtin_amdgcn_readlane(p2.z, q), __builtin_amdgcn_readlane(p2.w, q));
                                     a_hit = __builtin_amdgcn_readlane(ab, q) != 0u;
                                     break;
                                 }
@@ -3090,24 +2787,12 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                         // lanes from the limit on that meet a re-decided lane's target or action must speculate again
                         // (their validation assumed the re-decided lanes where they speculated: a kept one would
                         // keep a target whose room is gone or a rank that no longer holds)
-#if OWGS_COOP_CLASH
                         // (each such lane tests itself after barrier 9: the two sets go to LDS, one word per lane, in
-                        // the long-walk queue's first 512 bytes -- dead from barrier 3 to the next pass's speculation,
-                        // and the pre-walk results it holds in OWGS_PRE builds were last read by the loop above)
+                        // the long-walk queue's first 512 bytes -- dead from barrier 3 to the next pass's speculation)
                         if (nE > 0) {
                             ((uint32_t*)lq)[lane] = set_t;
                             ((uint32_t*)lq)[64 + lane] = set_a;
                         }
-#else
-                        if (nE > 0)
-                            for (int k0 = L; k0 < len; k0 += 64) {
-                                const int k = k0 + lane;
-                                uint4 f2 = make_uint4(FX_EXEMPT, FX_NOT, 0u, 0u);
-                                if (k < len) f2 = fxa[k];
-                                const bool cl = (inset(set_a, hsh(f2.x & OWGS_REC_NOACT)) | inset(set_t, hsh(f2.y & 0xFFFFu))) != 0u;
-                                if (k < len && !(f2.x & (FX_EXEMPT | FX_DONE)) && cl) fxa[k].x = f2.x | FX_CLASH;
-                            }
-#endif
                         st_ext += (uint32_t)nE;
 #ifdef OWGS_EXT_PROF
                         xp_cyc += memtime_pinned() - tx0;
@@ -3128,7 +2813,6 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                         s_t = (int)(fo.y >> 16);
                     }
                 }
-#endif
 #ifdef OWGS_STOP_REASONS
                 if (li == l && why) atomicAdd(&A.stats[6], 1ull << (12 * (why - 1)));
 #endif
@@ -3221,28 +2905,18 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                 const u64 tc1 = memtime_pinned();
 #endif
                 if (part) {
-#if OWGS_EXT
                     if (li >= l && cons && !fixup) atomicAdd(&P[t], cons);  // not committed: give the memory back
-#else
-                    if (li >= l && cons) atomicAdd(&P[t], cons);  // not committed: give the memory back
-#endif
                     fst[bk] = 0u;
                     bhead[bk] = 0u;
                 }
                 if (act && li >= l) {
                     keep = !nf;
-#if OWGS_EXT
-#if OWGS_COOP_CLASH
                     // (not exempt, never re-decided: li >= l) its own target and action against the published sets
                     if (keep && fixup && part && kind != K_FALLBACK && sc[SC_NEXT] > 0) {
                         const uint32_t h1 = hsh((uint32_t)t), h2 = hsh((uint32_t)a);
                         const uint32_t* sw = (const uint32_t*)lq;
                         if (((sw[h1 >> 5] >> (h1 & 31u)) | (sw[64 + (h2 >> 5)] >> (h2 & 31u))) & 1u) keep = false;
                     }
-#else
-                    if (keep && fixup && sc[SC_NEXT] > 0 && (fxa[li].x & FX_CLASH)) keep = false;
-#endif
-#endif
                     if (!keep && hs >= 0) hflag[hs] = l;  // the action's hot table is needed in the next pass
                     if (!keep && maxc > 1) cdirty[(par ^ 1) * OWGS_WL + lead] = 1;
                 }
@@ -3359,7 +3033,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
             atomicAdd(&A.stats[7], pt_x[1]);
         }
 #endif
-        if (io && lane == 0) atomicAdd(&A.stats[31], (u64)st_ext | ((u64)st_pre << 32));
+        if (io && lane == 0) atomicAdd(&A.stats[31], (u64)st_ext);  // (the upper half stays 0: it counted a retired path)
 #ifdef OWGS_EXT_PROF
         if (io && lane == 0) {
             atomicAdd(&A.stats[28], xp_cyc);
@@ -3704,7 +3378,8 @@ __global__ __launch_bounds__(64) void owgs_release_seq_kernel(OwgsReleaseArgs R)
 }
 
 // ------------------------------------------------------------------------------------------------ self-test
-// DPP scan / reduction helpers against a serial computation (one wave per trial)
+// DPP scan / reduction helpers against a serial computation (one wave per trial), and the engine's walk arithmetic
+// (owgs_device.h) against integer division, operands inside the forms' domains (owgs_divq.h)
 __global__ __launch_bounds__(64) void owgs_selftest_kernel(int* bad, int trials) {
     const int lane = threadIdx.x;
     for (int t = 0; t < trials; ++t) {
@@ -3718,11 +3393,12 @@ __global__ __launch_bounds__(64) void owgs_selftest_kernel(int* bad, int trials)
             ref_mx = max(ref_mx, vj);
         }
         if (inc != ref_inc || mx != ref_mx) atomicAdd(bad, 1);
-        // cap_of against integer division
-        const int m = 1 + (int)(h % 4096u), pv = (int)(ct_hash(h) % 5000000u);
-        const int cq = cap_of(pv, m, __builtin_amdgcn_rcpf((float)m));
-        const int ref = min(pv / m, CAPMAX);
-        if (cq != ref) atomicAdd(bad, 1);
+        // capacities: 0 <= pv < 2^22, 1 <= m <= 4096
+        const int m = 1 + (int)(h % 4096u), pv = (int)(ct_hash(h) % (uint32_t)OWGS_DIVQ_XMAX);
+        if (cap_q(pv, div_cap(m)) != min(pv / m, OWGS_CAPMAX)) atomicAdd(bad, 1);
+        // positions: 0 <= x < 2^31, 1 <= n < 2^15
+        const int x = (int)(ct_hash(h ^ 0x5bd1e995u) >> 1), n = 1 + (int)(ct_hash((uint32_t)pv) % 32767u);
+        if (pos_mod(x, div_pos(n, owgs_divq_magic((uint32_t)n))) != x % n) atomicAdd(bad, 1);
     }
 }
 

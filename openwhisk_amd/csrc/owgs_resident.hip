@@ -20,11 +20,10 @@
 // the host routes every other call to the chained path (owgs_host.cpp, res_eligible).
 #include <hip/hip_runtime.h>
 
+#include "owgs_device.h"
 #include "owgs_internal.h"
 #include "owgs_launch.h"
 #include "owgs_table.h"
-
-typedef unsigned long long u64;
 
 namespace {
 
@@ -33,28 +32,6 @@ __device__ __forceinline__ int ld_sys(const int32_t* p) {
 }
 __device__ __forceinline__ void st_sys(int32_t* p, int v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ u64 splitmix64(u64 x) {
-    x += 0x9E3779B97F4A7C15ULL;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
-    return x ^ (x >> 31);
-}
-// counter RNG replacing ThreadLocalRandom.nextInt(|H|) (SCPB:421): the engine's and the oracle's
-__device__ __forceinline__ uint32_t rng_index(u64 seed, u64 seq, uint32_t n) {
-    const u64 u = splitmix64(seed ^ (seq * 0x9E3779B97F4A7C15ULL)) >> 32;
-    return (uint32_t)((u * (u64)n) >> 32);
-}
-__device__ __forceinline__ int ffs64(u64 m) { return __ffsll((long long)m) - 1; }
-// x mod n for 0 <= x < 2^31, 1 <= n < 2^15 (float reciprocal, exact correction)
-__device__ __forceinline__ int mod_fast(int x, int n, float rn) {
-    const int q = (int)((float)x * rn);
-    int r = x - q * n;
-    r += r < 0 ? n : 0;
-    r += r < 0 ? n : 0;
-    r -= r >= n ? n : 0;
-    r -= r >= n ? n : 0;
-    return r;
 }
 __device__ __forceinline__ int wave_max_i(int v) {
 #pragma unroll
@@ -92,20 +69,6 @@ __device__ __forceinline__ void cc_put(uint2* cc, uint32_t a, uint32_t gen, int 
 #define SP_FORCED 3  // every pool position was full: the fallback's invoker, forced
 #define SP_STOP 4    // decided alone: concurrent, or the walk was not finished within the budget
 #define SP_FAIL 5    // (transient) the walk found no room anywhere
-
-// position of the need-th set bit of m (need < popc(m))
-__device__ __forceinline__ int select_in_word(uint32_t m, int need) {
-    int pos = 0;
-#pragma unroll
-    for (int w = 16; w >= 1; w >>= 1) {
-        const int c = __popc(m & ((1u << w) - 1u));
-        const bool up = need >= c;
-        need -= up ? c : 0;
-        m = up ? m >> w : m;
-        pos += up ? w : 0;
-    }
-    return pos;
-}
 
 #define RES_CC 2048  // walk-cursor cache entries (LDS, 16 KB)
 #define RES_BF 2048  // Bloom filter words over the primary table's keys (LDS, 8 KB)

@@ -21,25 +21,12 @@
 // table past half full, reports where, and the host grows the table and resumes there (owgs_host.cpp seq_run).
 #include <hip/hip_runtime.h>
 
+#include "owgs_device.h"
 #include "owgs_internal.h"
 #include "owgs_launch.h"
 
-typedef unsigned long long u64;
-
 namespace {
 
-__device__ __forceinline__ u64 splitmix64(u64 x) {
-    x += 0x9E3779B97F4A7C15ULL;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
-    return x ^ (x >> 31);
-}
-// the bench's counter RNG replacing ThreadLocalRandom.nextInt(|H|) (SCPB:421), as every engine and the oracle
-__device__ __forceinline__ uint32_t rng_index(u64 seed, u64 seq, uint32_t n) {
-    const u64 u = splitmix64(seed ^ (seq * 0x9E3779B97F4A7C15ULL)) >> 32;
-    return (uint32_t)((u * (u64)n) >> 32);
-}
-__device__ __forceinline__ int ffs64(u64 m) { return __ffsll((long long)m) - 1; }
 __device__ __forceinline__ int wave_sum(int v) {  // (every lane gets the wave's sum)
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);

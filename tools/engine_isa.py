@@ -15,9 +15,17 @@ Each file is compiled three times: as the library builds it (both roles in one k
 regions, twice: by the phase of the engine body it was inlined into (the outermost frame of its location: the body's
 marker comments and a few anchor lines split it), and by the function its own line lies in (the innermost frame: the
 inlined helpers).  Same columns per region; regions without instructions are left out.
+
+--identity PARENT_PKG compares this tree with another checkout's openwhisk_amd/ instead (the check of a refactor): every
+.hip file under csrc/ of both trees is compiled with the Makefile's flags for that file, and per kernel symbol the
+instruction text (comments dropped, the function index of local labels normalised) and the .amdhsa_kernel descriptor
+are compared.  One line per kernel: identical / differs, then the kernels only one tree has; identical kernels of the
+libraries (rocprim instantiations) are only counted.
 """
 import argparse
 import concurrent.futures as cf
+import difflib
+import hashlib
 import os
 import re
 import subprocess
@@ -49,7 +57,7 @@ BODY_ANCHORS = [
     (r"if \(maxc == 1 && pool_mode == 0\) \{", "lanes' walks: plain 4-step groups"),
     (r"if \(maxc > 1 && pool_mode == 0\) \{", "lanes' walks: concurrent 4-step groups"),
     (r"for \(int k = 0; k < KPROBE_G; \+\+k\) \{", "lanes' walks: general walk"),
-    (r"if \(!done\) done = mm >", "re-decisions: walk"),
+    (r"bool done = mm >", "re-decisions: walk"),
     (r"if \(!done\) break;  // a long walk", "re-decisions: after the walk"),
     (r"if \(act && li >= l0 && li < l\) \{", "commit: decisions of lanes [f, l)"),
     (r"if \(act && li >= l\) \{", "commit: lanes from l on"),
@@ -246,13 +254,108 @@ def parse_remarks(text):
     return out
 
 
+def file_flags(pkg):
+    """(hipcc, flags of one csrc/NAME.hip as a function of NAME) from one reading of the Makefile: HIPFLAGS, plus
+    ENGINEFLAGS for the files whose build/NAME.o is a target of the ENGINEFLAGS assignment."""
+    hipcc, both = makefile_flags(pkg)
+    m = re.search(r"^([^\n#=]+):[ \t]*ENGINEFLAGS[ \t]*:=[ \t]*(.*)$", open(os.path.join(pkg, "Makefile")).read(), re.M)
+    targets, eng = (m.group(1).split(), m.group(2).split()) if m else ([], [])
+    # makefile_flags returns HIPFLAGS followed by ENGINEFLAGS: the plain flags are that list without its tail
+    assert both[len(both) - len(eng):] == eng, "ENGINEFLAGS is expected at the end of makefile_flags()"
+    plain = both[:len(both) - len(eng)]
+    return hipcc, lambda src: both if f"build/{os.path.splitext(src)[0]}.o" in targets else plain
+
+
+def compile_one(pkg, hipcc, flags, src, out):
+    cmd = [hipcc] + flags + ["--cuda-device-only", "-S", "-o", out, os.path.join("csrc", src)]
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=pkg)
+    if r.returncode != 0:
+        sys.stderr.write(r.stderr)
+        raise SystemExit(f"{src}: compile failed")
+    return open(out).read()
+
+
+def kernel_texts(asm):
+    """{kernel symbol: (code lines, descriptor lines)}: the text between the symbol's label and its .Lfunc_end without
+    comments, the function index in local labels dropped (.LBB<i>_<n> -> .LBB_<n>), and its .amdhsa_kernel block."""
+    lines = asm.splitlines()
+    desc, cur = {}, None
+    for line in lines:
+        m = re.match(r"^\s*\.amdhsa_kernel\s+(\S+)", line)
+        if m:
+            cur = desc.setdefault(m.group(1), [])
+        elif re.match(r"^\s*\.end_amdhsa_kernel", line):
+            cur = None
+        elif cur is not None:
+            cur.append(" ".join(line.split(";", 1)[0].split()))
+    out, cur = {}, None
+    for line in lines:
+        if cur is None:
+            m = re.match(r"^(\w+):", line)
+            if m and m.group(1) in desc:
+                cur = out.setdefault(m.group(1), [])
+            continue
+        if line.startswith(".Lfunc_end"):
+            cur = None
+            continue
+        t = " ".join(line.split(";", 1)[0].split())
+        if t:
+            cur.append(re.sub(r"(\.L[A-Za-z_]+)\d+_", r"\1_", t))
+    return {k: (out.get(k, []), d) for k, d in desc.items()}
+
+
+def identity(new_pkg, old_pkg):
+    """Compare every kernel of every csrc/*.hip of two trees, each file compiled with its own tree's flags."""
+    with tempfile.TemporaryDirectory() as d, cf.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+        futs = []
+        for side, pkg in (("new", new_pkg), ("parent", old_pkg)):
+            hipcc, flags_of = file_flags(pkg)
+            for src in sorted(f for f in os.listdir(os.path.join(pkg, "csrc")) if f.endswith(".hip")):
+                futs.append((side, src, ex.submit(compile_one, pkg, hipcc, flags_of(src), src, os.path.join(d, f"{side}_{src}.s"))))
+        found = {"new": {}, "parent": {}}
+        for side, src, f in futs:
+            for k, v in kernel_texts(f.result()).items():
+                found[side].setdefault(k, []).append((src, v))
+    # (library kernels are weak and instantiated in every file that uses them: a symbol found twice goes by file too)
+    twice = {k for side in found for k, defs in found[side].items() if len(defs) > 1}
+    kern = {side: {(f"{k} @{src}" if k in twice else k): (src, v) for k, defs in found[side].items() for src, v in defs}
+            for side in found}
+    def show(k):  # (library template instantiations run to a kilobyte: their head and a digest of the whole name)
+        return k if len(k) <= 160 else f"{k[:120]}...#{hashlib.md5(k.encode()).hexdigest()[:8]}"
+    n_same = n_diff = n_lib = 0
+    for k in sorted(set(kern["new"]) & set(kern["parent"])):
+        (sn, vn), (sp, vp) = kern["new"][k], kern["parent"][k]
+        same = vn == vp
+        n_same += same
+        n_diff += not same
+        if same and re.match(r"_ZN(7rocprim|6hipcub)", k):  # a library (rocprim) kernel: counted, listed only when it differs
+            n_lib += 1
+            continue
+        what = "identical" if same else ("differs (code)" if vn[0] != vp[0] else "differs (descriptor)")
+        if vn[0] != vp[0]:  # how far apart: lines on each side, and the lines a diff takes out of / puts into the parent's
+            d = [x for x in difflib.unified_diff(vp[0], vn[0], lineterm="", n=0) if x[:1] in "+-" and x[:3] not in ("+++", "---")]
+            what += f" {len(vp[0])} -> {len(vn[0])} lines, -{sum(x[0] == '-' for x in d)} +{sum(x[0] == '+' for x in d)}"
+        print(f"{what:22s} {show(k)}  [{sn}{'' if sn == sp else ' <- ' + sp}]")
+    only_p = sorted(set(kern["parent"]) - set(kern["new"]))
+    only_n = sorted(set(kern["new"]) - set(kern["parent"]))
+    for k in only_p:
+        print(f"{'parent only':22s} {show(k)}  [{kern['parent'][k][0]}]")
+    for k in only_n:
+        print(f"{'new only':22s} {show(k)}  [{kern['new'][k][0]}]")
+    print(f"# {n_same} identical ({n_lib} of them library kernels, not listed), {n_diff} differ, {len(only_p)} parent only, "
+          f"{len(only_n)} new only")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--src", default=os.path.join(HERE, "..", "openwhisk_amd"), help="the openwhisk_amd/ directory to read")
     ap.add_argument("--only-kernel", default="owgs_engine_kernel", help="substring of the kernels to print ('' = all three)")
     ap.add_argument("--regions", action="store_true", help="attribute the role builds' instructions to source regions")
+    ap.add_argument("--identity", metavar="PARENT_PKG", help="compare every kernel's code with another checkout's openwhisk_amd/")
     a = ap.parse_args()
     pkg = os.path.abspath(a.src)
+    if a.identity:
+        return identity(pkg, os.path.abspath(a.identity))
     builds = [("both roles", []), ("engine waves", ["-DOWGS_ROLE_ONLY=0"]), ("I/O wave", ["-DOWGS_ROLE_ONLY=1"])]
     srcs = ["owgs_kernels.hip", "owgs_engine_narrow.hip"]
     extra_of = dict(builds)
