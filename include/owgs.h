@@ -371,10 +371,10 @@ int owgs_set_throttle_limits(owgs_ctx* ctx, int32_t invokes_per_minute, int32_t 
 
 /* The gate over n items.  An override array may be NULL when no item sets its kind bit.  t_ms in [0, 2^60).
  * out_rate_limit / out_conc_limit are the computed limits (Messages.tooManyRequests(count, allowed); the
- * ConcurrentInvocations metric is conc_count + 1, Entitlement.scala:389-391); out_conc_limit is written for every
- * action, also when its concurrent check was skipped.  ns[i] = OWGS_NONE, a reserved kind bit, a kind bit without
- * its array or a t_ms outside the range return OWGS_EINVAL, an unknown handle OWGS_ENOENT, all before any state
- * changes. */
+ * ConcurrentInvocations metric is conc_count + 1, Entitlement.scala:389-391; owgs_throttle_events below prints both
+ * from these outputs); out_conc_limit is written for every action, also when its concurrent check was skipped.
+ * ns[i] = OWGS_NONE, a reserved kind bit, a kind bit without its array or a t_ms outside the range return
+ * OWGS_EINVAL, an unknown handle OWGS_ENOENT, all before any state changes. */
 int owgs_admit_batch(owgs_ctx* ctx, int32_t n, const int32_t* ns, const uint8_t* kind, const int64_t* t_ms,
                      const int32_t* rate_override, const int32_t* conc_override, uint8_t* out_verdict,
                      int32_t* out_rate_count, int32_t* out_rate_limit, int32_t* out_conc_count,
@@ -803,6 +803,99 @@ typedef struct owgs_invoke_io {
 
 int owgs_invoke_activations(owgs_ctx* ctx, const owgs_invoke_io* io, const owgs_msg_batch* msgs, owgs_msg_out* mo,
                             int64_t out_summary[16]);
+
+/* ---- throttle gate: user-event messages and rejection texts ----
+ * Replaces: the two per-item outputs of checkThrottleOverload (Entitlement.scala:383-420) for a drained batch -- the
+ * EventMessage it sends to the topic `events` for every admitted action invoke (Metric("ConcurrentInvocations", count
+ * + 1)) and for every rejected invoke or fire (Metric(limit.limitName, 1)), and the text the rejected request fails with
+ * (limit.errorMsg: ActivationThrottler.scala:58-67, ErrorResponse.scala:70-75).  Both are pure functions of the gate's
+ * outputs for the item (owgs_admit_batch, unchanged) and of a timestamp.
+ *
+ * Setup state of a context, both additive:
+ *   - the event source: one printed JSON string value with its quotes, e.g. "controller0"
+ *     (s"controller${controllerInstance.asString}", Entitlement.scala:395, 411); unset until owgs_set_event_source.
+ *   - event identities, append-only, ids from 0: two opaque byte pieces the caller prints once per Identity with
+ *     spray-json (escaping is the caller's): piece A = `"subject":<string>`, piece B =
+ *     `"userId":<string>,"namespace":<string>`.  Any length >= 0.
+ *
+ * Item i, in array order, with S the source, A / B the pieces of ident[i] and ts = ts_ms[i]:
+ *   action,  verdict OWGS_ADMIT_OK          event ConcurrentInvocations, value (int64)(int32)(conc_count[i] + 1) -- the
+ *                                           reference adds 1 to an Int (wrapping) and then widens; no text
+ *   trigger, verdict OWGS_ADMIT_OK          no event (`case _ => // ignore`), no text
+ *   verdict OWGS_ADMIT_RATE (either kind)   event TimedRateLimit, value 1; text
+ *                                           `Too many requests in the last minute (count: <rate_count>, allowed: <rate_limit>).`
+ *   verdict OWGS_ADMIT_CONCURRENT           event ConcurrentRateLimit, value 1; text
+ *                                           `Too many concurrent requests in flight (count: <conc_count>, allowed: <conc_limit>).`
+ * Event bytes (EventMessage.serialize = format.write(this).compactPrint, Message.scala:404-418):
+ *   {"body":{"metricName":"<name>","metricValue":<v>},"eventType":"Metric","source":S,A,"timestamp":<ts>,B}
+ * Numbers are plain decimal with a leading '-' when negative; the texts print signed 32-bit values, <v> and <ts> signed
+ * 64-bit ones.  Member order: spray-json 1.3.5 builds a JsObject from Map(fields: _*); seven members make a Scala 2.12
+ * immutable HashMap, whose iteration order (String.hashCode, improve, 5 bits per trie level from the low end) is body,
+ * eventType, source, subject, timestamp, userId, namespace -- the order of the reference's own example
+ * (docs/metrics.md:353-364); the two-member body keeps insertion order (Map2).
+ * Timestamp: the reference takes System.currentTimeMillis() when it constructs the message, right after the check;
+ * here it is ts_ms[i], which the integrated call takes from t_ms[i], the time of the item's check.
+ *
+ * Outputs are BY ITEM: event i is ev_out[ev_off[i] .. ev_off[i+1]), text i is rej_out[rej_off[i] .. rej_off[i+1]); an
+ * item without an event or text has an empty range.  There is one topic, and item order is send order. */
+#define OWGS_EVENT_NAME_MAX 21 /* strlen("ConcurrentInvocations"), the longest metric name */
+/* The largest event without S, A and B: the literals, the longest name, an int32 value with its sign (the int64 value
+ * is a widened int32, or 1) and an int64 timestamp with its sign. */
+#define OWGS_EVENT_MAX_FIXED                                                                                         \
+    ((int64_t)(sizeof("{\"body\":{\"metricName\":\"\",\"metricValue\":},\"eventType\":\"Metric\",\"source\":,,"      \
+                      "\"timestamp\":,}") - 1) + OWGS_EVENT_NAME_MAX + 11 + 20)
+/* The largest rejection text: the longer literal and two int32 values with their signs. */
+#define OWGS_REJECT_TEXT_MAX \
+    ((int64_t)(sizeof("Too many concurrent requests in flight (count: , allowed: ).") - 1) + 11 + 11)
+/* So ev_cap = n * (OWGS_EVENT_MAX_FIXED + |S| + max |A| + max |B|) and rej_cap = n * OWGS_REJECT_TEXT_MAX always
+ * suffice. */
+
+int owgs_set_event_source(owgs_ctx* ctx, const char* json, int32_t len);
+/* Identities append; returns the id of the first new one.  Offsets that do not start at 0 or that decrease:
+ * OWGS_EINVAL. */
+int owgs_register_event_identities(owgs_ctx* ctx, int32_t n, const char* a_bytes, const int64_t* a_off,
+                                   const char* b_bytes, const int64_t* b_off, int32_t* out_first_id);
+
+typedef struct owgs_event_io {
+    const int32_t* ident;          /* [n] event identity per item */
+    char* ev_out;                  /* host buffers */
+    int64_t ev_cap;
+    int64_t* ev_off;               /* [n + 1] */
+    char* rej_out;
+    int64_t rej_cap;
+    int64_t* rej_off;              /* [n + 1] */
+    int64_t ev_total, rej_total;   /* written by the call: bytes needed */
+    int32_t n_events, n_rejects;   /* ... and items with an event / a text */
+} owgs_event_io;
+
+/* The pure function above over host arrays (the outputs of owgs_admit_batch, or of an earlier
+ * owgs_invoke_activations_events whose event stage was refused for capacity); no state changes.  kind: only bit 0
+ * (OWGS_ADMIT_TRIGGER) matters, the override bits are accepted.  rate_count / rate_limit are read for OWGS_ADMIT_RATE
+ * items, conc_count for admitted actions and OWGS_ADMIT_CONCURRENT items, conc_limit for the latter.
+ * OWGS_EINVAL: a NULL among ctx, ev, and with n > 0 the nine arrays, ev->ident, ev->ev_off, ev->rej_off (ev_out /
+ * rej_out may be NULL with a cap of 0); n < 0; a negative cap; the event source not set; a verdict outside 0..2; a
+ * reserved kind bit.  OWGS_ENOENT: an ident[i] outside the registered range (every item is checked, whether or not it
+ * has an event).  n == 0 is OWGS_OK with totals 0.
+ * Capacity: ev_total > ev_cap or rej_total > rej_cap leaves THAT region (its bytes) untouched, the other region is still
+ * written; both offset arrays, both totals and both counts are set, and the call returns OWGS_ERANGE. */
+int owgs_throttle_events(owgs_ctx* ctx, int32_t n, const uint8_t* kind, const uint8_t* verdict,
+                         const int32_t* rate_count, const int32_t* rate_limit, const int32_t* conc_count,
+                         const int32_t* conc_limit, const int64_t* ts_ms, owgs_event_io* ev);
+
+/* owgs_invoke_activations -- everything it does and returns, unchanged -- plus the events and texts of the batch, built
+ * on the device from the gate's outputs (ts = io->t_ms) right after the gate; the two offset arrays, totals and counts
+ * come back in the call's one block copy, the bytes are downloaded like the message bytes (not counted in [12]).
+ * ev == NULL behaves exactly as owgs_invoke_activations.
+ * out_summary: [0..12] as owgs_invoke_activations; [13] events written, [14] rejection texts written (each 0 when its
+ * region was refused); [15] the event stage: 0 not asked, 1 done, 2 refused for capacity.
+ * Failures: every argument error of owgs_invoke_activations and of owgs_throttle_events' ev (NULLs, a negative cap, the
+ * source not set: OWGS_EINVAL; an unknown ident[i]: OWGS_ENOENT) is refused before any state changes, the rate records
+ * included.  A region over its cap is left untouched and the other is written, as in owgs_throttle_events: [15] = 2 and
+ * OWGS_ERANGE, while every gate and publish output is valid and every state change stands; the caller repeats only
+ * owgs_throttle_events with larger buffers.  If the message stage fails too its code wins; [6] and [15] carry both
+ * facts.  When the engine step fails and only the gate outputs are handed out, the events are handed out with them. */
+int owgs_invoke_activations_events(owgs_ctx* ctx, const owgs_invoke_io* io, const owgs_msg_batch* msgs,
+                                   owgs_msg_out* mo, owgs_event_io* ev, int64_t out_summary[16]);
 
 /* Duration of the last owgs_engine_kernel launch (HIP events recorded on its stream right before and after it);
  * waits for it to finish.  Measurement hook for bench.py's roofline. */

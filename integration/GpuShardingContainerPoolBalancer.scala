@@ -69,6 +69,21 @@ object OwgsNative {
    *  for a rejected item; the publishes' overload-RNG sequence numbers are seqBase + the rank among the admitted
    *  actions.  For an EntitlementProvider that defers checkThrottles to the batching thread (INTEGRATION.md). */
   @native def invokeActivations(ctx: Long, in: ByteBuffer, out: ByteBuffer, n: Int, seqBase: Long, nowMs: Long): Int
+  /** owgs_set_event_source: EventMessage.source printed as a JSON string with its quotes,
+   *  JsString(s"controller${controllerInstance.asString}").compactPrint as UTF-8 (Entitlement.scala:395, 411). */
+  @native def setEventSource(ctx: Long, json: Array[Byte]): Int
+  /** owgs_register_event_identities: per Identity the members of its user events, printed once with spray-json:
+   *  a = "subject":<string>, b = "userId":<string>,"namespace":<string>; offsets as registerTemplates'.  Returns the
+   *  id of the first new identity. */
+  @native def registerEventIdentities(ctx: Long, a: Array[Byte], aOff: Array[Long], b: Array[Byte], bOff: Array[Long],
+                                      n: Int): Int
+  /** owgs_invoke_activations_events (msgs = NULL): invokeActivations plus, built on the device from the gate's
+   *  verdicts and counts, the EventMessage checkThrottleOverload sends to `events` for every admitted action invoke and
+   *  every rejected item (Entitlement.scala:383-420), and the rejected items' error texts; layout in EventBuffers.
+   *  Item order is send order.  OWGS_ERANGE (-34) with summary(15) == 2: a region did not fit, everything else is
+   *  done; the totals are in evOut. */
+  @native def invokeActivationsEvents(ctx: Long, in: ByteBuffer, out: ByteBuffer, evIn: ByteBuffer, evOut: ByteBuffer,
+                                      n: Int, evCap: Long, rejCap: Long, seqBase: Long, nowMs: Long): Int
   /** owgs_release_actions: handles of cold fqn@version keys (none of their activations in flight) */
   @native def releaseActions(ctx: Long, handles: Array[Int], n: Int): Int
   /** owgs_track_activations_timed: setupActivation's getOrElseUpdate with the entry's invoker and time limit, so that
@@ -180,6 +195,28 @@ final class InvokeBuffers {
   def ensure(n: Int): Unit = {
     if (in.capacity < 53 * n) in = ByteBuffer.allocateDirect(106 * n).order(ByteOrder.nativeOrder())
     if (out.capacity < 128 + 27 * n) out = ByteBuffer.allocateDirect(256 + 54 * n).order(ByteOrder.nativeOrder())
+  }
+}
+
+/** The two further direct buffers of one invokeActivationsEvents call (owgs_jni.c reads the same layout):
+ *  evIn  = ident[n] (ints), the event identity of each item;
+ *  evOut = evTotal, rejTotal, nEvents, nRejects (longs), evOff[n + 1], rejOff[n + 1] (longs), then evCap bytes of events
+ *          and rejCap bytes of rejection texts.  Event i is evOff(i) until evOff(i + 1) of the event region (empty for
+ *          an admitted trigger), text i likewise.  pieceBytes = source + the longest pieces a and b registered; the
+ *          two constants are OWGS_EVENT_MAX_FIXED and OWGS_REJECT_TEXT_MAX of include/owgs.h. */
+final class EventBuffers(pieceBytes: Int) {
+  val EventMaxFixed = 139L
+  val RejectTextMax = 82L
+  var evIn: ByteBuffer = ByteBuffer.allocateDirect(1 << 12).order(ByteOrder.nativeOrder())
+  var evOut: ByteBuffer = ByteBuffer.allocateDirect(1 << 16).order(ByteOrder.nativeOrder())
+  def evCap(n: Int): Long = n * (EventMaxFixed + pieceBytes)
+  def rejCap(n: Int): Long = n * RejectTextMax
+  def eventsAt(n: Int): Int = 32 + 16 * (n + 1)
+  def textsAt(n: Int): Int = (eventsAt(n) + evCap(n)).toInt
+  def ensure(n: Int): Unit = {
+    val need = eventsAt(n) + evCap(n) + rejCap(n)
+    if (evIn.capacity < 4 * n) evIn = ByteBuffer.allocateDirect(8 * n).order(ByteOrder.nativeOrder())
+    if (evOut.capacity < need) evOut = ByteBuffer.allocateDirect((2 * need).toInt).order(ByteOrder.nativeOrder())
   }
 }
 

@@ -170,6 +170,32 @@ JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00
  * out = summary[16] (int64), rate_count[n], rate_limit[n], conc_count[n], conc_limit[n], out_invoker[n], out_ticket[n]
  *       (int32), verdict[n], out_flags[n], out_existed[n] (bytes).
  * Sequence numbers: seq_base + the rank among the admitted actions (the shim numbers what it publishes). */
+static void invoke_io_fill(owgs_invoke_io* io, char* pi, char* po, jint n, jlong seq_base, jlong now_ms) {
+    memset(io, 0, sizeof *io);
+    io->n = n;
+    io->aid = (const uint64_t*)pi;
+    io->time_limit_ms = (const int64_t*)(pi + 16 * (jlong)n);
+    io->t_ms = io->time_limit_ms + n;
+    io->action = (const int32_t*)(pi + 32 * (jlong)n);
+    io->ns = io->action + n;
+    io->ticket = io->action + 2 * (jlong)n;
+    io->rate_override = io->action + 3 * (jlong)n;
+    io->conc_override = io->action + 4 * (jlong)n;
+    io->kind = (const uint8_t*)(pi + 52 * (jlong)n);
+    io->seq = NULL;
+    io->seq_base = (uint64_t)seq_base;
+    io->now_ms = now_ms;
+    io->out_rate_count = (int32_t*)(po + 128);
+    io->out_rate_limit = io->out_rate_count + n;
+    io->out_conc_count = io->out_rate_count + 2 * (jlong)n;
+    io->out_conc_limit = io->out_rate_count + 3 * (jlong)n;
+    io->out_invoker = io->out_rate_count + 4 * (jlong)n;
+    io->out_ticket = io->out_rate_count + 5 * (jlong)n;
+    io->out_verdict = (uint8_t*)(po + 128 + 24 * (jlong)n);
+    io->out_flags = io->out_verdict + n;
+    io->out_existed = io->out_verdict + 2 * (jlong)n;
+}
+
 JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_invokeActivations(
     JNIEnv* env, jobject self, jlong h, jobject in, jobject out, jint n, jlong seq_base, jlong now_ms) {
     if (!in || !out || n < 0) return OWGS_EINVAL;
@@ -180,30 +206,52 @@ JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00
         (*env)->GetDirectBufferCapacity(env, out) < 128 + 27 * (jlong)n)
         return OWGS_EINVAL;
     owgs_invoke_io io;
-    memset(&io, 0, sizeof io);
-    io.n = n;
-    io.aid = (const uint64_t*)pi;
-    io.time_limit_ms = (const int64_t*)(pi + 16 * (jlong)n);
-    io.t_ms = io.time_limit_ms + n;
-    io.action = (const int32_t*)(pi + 32 * (jlong)n);
-    io.ns = io.action + n;
-    io.ticket = io.action + 2 * (jlong)n;
-    io.rate_override = io.action + 3 * (jlong)n;
-    io.conc_override = io.action + 4 * (jlong)n;
-    io.kind = (const uint8_t*)(pi + 52 * (jlong)n);
-    io.seq = NULL;
-    io.seq_base = (uint64_t)seq_base;
-    io.now_ms = now_ms;
-    io.out_rate_count = (int32_t*)(po + 128);
-    io.out_rate_limit = io.out_rate_count + n;
-    io.out_conc_count = io.out_rate_count + 2 * (jlong)n;
-    io.out_conc_limit = io.out_rate_count + 3 * (jlong)n;
-    io.out_invoker = io.out_rate_count + 4 * (jlong)n;
-    io.out_ticket = io.out_rate_count + 5 * (jlong)n;
-    io.out_verdict = (uint8_t*)(po + 128 + 24 * (jlong)n);
-    io.out_flags = io.out_verdict + n;
-    io.out_existed = io.out_verdict + 2 * (jlong)n;
+    invoke_io_fill(&io, pi, po, n, seq_base, now_ms);
     return owgs_invoke_activations(CTX(h), &io, NULL, NULL, (int64_t*)po);
+}
+
+/* invokeActivations plus the user events and rejection texts of the batch (owgs_invoke_activations_events, msgs =
+ * NULL).  in / out as InvokeBuffers; two more direct buffers, layout as EventBuffers in the Scala shim:
+ * ev_in  = ident[n] (int32), the event identity of each item;
+ * ev_out = ev_total, rej_total, n_events, n_rejects (int64), ev_off[n + 1], rej_off[n + 1] (int64), then ev_cap bytes of
+ *          events and rej_cap bytes of texts.  Event i is the bytes ev_off[i] .. ev_off[i + 1] of the event region.
+ * Returns OWGS_ERANGE with the totals set when a region does not fit (summary[15] = 2): everything else is done. */
+JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_invokeActivationsEvents(
+    JNIEnv* env, jobject self, jlong h, jobject in, jobject out, jobject ev_in, jobject ev_out, jint n, jlong ev_cap,
+    jlong rej_cap, jlong seq_base, jlong now_ms) {
+    if (!in || !out || !ev_in || !ev_out || n < 0 || ev_cap < 0 || rej_cap < 0) return OWGS_EINVAL;
+    char* pi = (char*)(*env)->GetDirectBufferAddress(env, in);
+    char* po = (char*)(*env)->GetDirectBufferAddress(env, out);
+    char* ei = (char*)(*env)->GetDirectBufferAddress(env, ev_in);
+    char* eo = (char*)(*env)->GetDirectBufferAddress(env, ev_out);
+    if (!pi || !po || !ei || !eo) return OWGS_EINVAL;  /* not direct buffers */
+    const jlong head = 32 + 16 * ((jlong)n + 1);
+    if (ev_cap > INT64_MAX - head || rej_cap > INT64_MAX - head - ev_cap) return OWGS_EINVAL;
+    if ((*env)->GetDirectBufferCapacity(env, in) < 53 * (jlong)n ||
+        (*env)->GetDirectBufferCapacity(env, out) < 128 + 27 * (jlong)n ||
+        (*env)->GetDirectBufferCapacity(env, ev_in) < 4 * (jlong)n ||
+        (*env)->GetDirectBufferCapacity(env, ev_out) < head + ev_cap + rej_cap)
+        return OWGS_EINVAL;
+    owgs_invoke_io io;
+    invoke_io_fill(&io, pi, po, n, seq_base, now_ms);
+    owgs_event_io ev;
+    memset(&ev, 0, sizeof ev);
+    ev.ident = (const int32_t*)ei;
+    ev.ev_off = (int64_t*)(eo + 32);
+    ev.rej_off = ev.ev_off + n + 1;
+    ev.ev_out = eo + head;
+    ev.ev_cap = ev_cap;
+    ev.rej_out = eo + head + ev_cap;
+    ev.rej_cap = rej_cap;
+    const int rc = owgs_invoke_activations_events(CTX(h), &io, NULL, NULL, &ev, (int64_t*)po);
+    if (rc == OWGS_OK || rc == OWGS_ERANGE) {
+        int64_t* w = (int64_t*)eo;
+        w[0] = ev.ev_total;
+        w[1] = ev.rej_total;
+        w[2] = ev.n_events;
+        w[3] = ev.n_rejects;
+    }
+    return rc;
 }
 
 /* handles of cold fqn@version keys (owgs_release_actions) */
@@ -600,6 +648,40 @@ JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00
     int32_t first = 0;
     int rc = OWGS_ENOMEM;
     if (pa && pb) rc = owgs_register_templates(CTX(h), n, pa, pao, pb, pbo, &first);
+    FREE_ALL(pao, pbo, pa, pb);
+    return rc == OWGS_OK ? first : rc;
+}
+
+/* ---- throttle gate events: the source and the identities' printed members ---- */
+JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_setEventSource(
+    JNIEnv* env, jobject self, jlong h, jbyteArray json) {
+    if (!json) return OWGS_EINVAL;
+    const jlong n = (*env)->GetArrayLength(env, json);
+    if (n > INT32_MAX) return OWGS_EINVAL;
+    char* p = jcopy_in(env, json, n, 1, 'B');
+    const int rc = p ? owgs_set_event_source(CTX(h), p, (int32_t)n) : OWGS_ENOMEM;
+    free(p);
+    return rc;
+}
+
+JNIEXPORT jint JNICALL Java_org_apache_openwhisk_core_loadBalancer_OwgsNative_00024_registerEventIdentities(
+    JNIEnv* env, jobject self, jlong h, jbyteArray a, jlongArray aOff, jbyteArray b, jlongArray bOff, jint n) {
+    if (!a || !aOff || !b || !bOff || !n_fits(env, (jlong)n + 1, aOff, bOff, NULL, NULL)) return OWGS_EINVAL;
+    int64_t* pao = jcopy_in(env, aOff, (jlong)n + 1, 8, 'J');
+    int64_t* pbo = jcopy_in(env, bOff, (jlong)n + 1, 8, 'J');
+    if (!pao || !pbo) {
+        FREE_ALL(pao, pbo);
+        return OWGS_ENOMEM;
+    }
+    if (pao[n] > (*env)->GetArrayLength(env, a) || pbo[n] > (*env)->GetArrayLength(env, b)) {
+        FREE_ALL(pao, pbo);
+        return OWGS_EINVAL;
+    }
+    char* pa = jcopy_in(env, a, (*env)->GetArrayLength(env, a), 1, 'B');
+    char* pb = jcopy_in(env, b, (*env)->GetArrayLength(env, b), 1, 'B');
+    int32_t first = 0;
+    int rc = OWGS_ENOMEM;
+    if (pa && pb) rc = owgs_register_event_identities(CTX(h), n, pa, pao, pb, pbo, &first);
     FREE_ALL(pao, pbo, pa, pb);
     return rc == OWGS_OK ? first : rc;
 }

@@ -33,6 +33,10 @@ NS_INITIAL_CAP = 1024  # OWGS_NS_INITIAL_CAP: namespaces the device counter arra
 ADMIT_OK, ADMIT_RATE, ADMIT_CONCURRENT = 0, 1, 2  # owgs_admit_batch verdicts
 ADMIT_TRIGGER, ADMIT_RATE_OVERRIDE, ADMIT_CONC_OVERRIDE = 1, 2, 4  # ... and its kind bits
 RATE_ABSENT = -2**63  # owgs_rate_state: no record yet
+# owgs_throttle_events: the largest event without source and identity pieces, the largest rejection text
+EVENT_NAME_MAX = 21
+EVENT_MAX_FIXED = len('{"body":{"metricName":"","metricValue":},"eventType":"Metric","source":,,"timestamp":,}') + 21 + 11 + 20
+REJECT_TEXT_MAX = len("Too many concurrent requests in flight (count: , allowed: ).") + 11 + 11
 
 
 class OwgsError(RuntimeError):
@@ -83,6 +87,13 @@ class owgs_invoke_io(C.Structure):
                 ("out_rate_count", C.c_void_p), ("out_rate_limit", C.c_void_p), ("out_conc_count", C.c_void_p),
                 ("out_conc_limit", C.c_void_p), ("out_invoker", C.c_void_p), ("out_flags", C.c_void_p),
                 ("out_ticket", C.c_void_p), ("out_existed", C.c_void_p)]
+
+
+class owgs_event_io(C.Structure):
+    """include/owgs.h: owgs_event_io (the identities, the two host regions and what the call writes about them)."""
+    _fields_ = [("ident", C.c_void_p), ("ev_out", C.c_void_p), ("ev_cap", C.c_int64), ("ev_off", C.c_void_p),
+                ("rej_out", C.c_void_p), ("rej_cap", C.c_int64), ("rej_off", C.c_void_p), ("ev_total", C.c_int64),
+                ("rej_total", C.c_int64), ("n_events", C.c_int32), ("n_rejects", C.c_int32)]
 
 
 class owgs_ack_out(C.Structure):
@@ -146,6 +157,10 @@ def lib() -> C.CDLL:
         "owgs_serialize_activations_device": (C.c_int, [P, P, i32, P, C.c_int64, P, P, P, P, P, P]),
         "owgs_publish_activations": (C.c_int, [P, P, P, P, P]),
         "owgs_invoke_activations": (C.c_int, [P, P, P, P, P]),
+        "owgs_set_event_source": (C.c_int, [P, C.c_char_p, i32]),
+        "owgs_register_event_identities": (C.c_int, [P, i32, P, P, P, P, P]),
+        "owgs_throttle_events": (C.c_int, [P, i32, P, P, P, P, P, P, P, P]),
+        "owgs_invoke_activations_events": (C.c_int, [P, P, P, P, P, P]),
         "owgs_health_read": (C.c_int, [P, i32, P, P, P, P, P, P]),
         "owgs_process_pings": (C.c_int, [P, i32, P, P, P, C.c_int64, i32, P, P, P, P]),
         "owgs_process_acks_supervised": (C.c_int, [P, i32, P, P, P, P, P, P, C.c_int64, i32, P]),

@@ -382,6 +382,80 @@ class GpuShardingContainerPoolBalancer:
         self._chk(self._L.owgs_set_throttle_limits(self._h, invokes_per_minute, fires_per_minute,
                                                    concurrent_invocations))
 
+    # ------------------------------------------------------------------ throttle gate events
+    def set_event_source(self, json_value: str):
+        """EventMessage.source as a printed JSON string with its quotes, e.g. '"controller0"' (Entitlement.scala:395)."""
+        b = json_value.encode()
+        self._chk(self._L.owgs_set_event_source(self._h, b, len(b)))
+        self._ev_fixed = len(b)
+
+    def register_event_identities(self, part_a, part_b) -> int:
+        """The members of an EventMessage that belong to the Identity, printed once by the caller (str or bytes):
+        part A = '"subject":<string>', part B = '"userId":<string>,"namespace":<string>'.  Returns the first new id."""
+        if len(part_a) != len(part_b):
+            raise ValueError("register_event_identities: one piece A and one piece B per identity")
+        ab, ao = _blob(part_a)
+        bb, bo = _blob(part_b)
+        first = C.c_int32(0)
+        self._chk(self._L.owgs_register_event_identities(self._h, len(part_a), _p(ab), _p(ao), _p(bb), _p(bo),
+                                                         C.byref(first)))
+        if len(part_a):
+            self._ev_piece = max(getattr(self, "_ev_piece", 0), int(np.max(np.diff(ao)) + np.max(np.diff(bo))))
+        return first.value
+
+    def _event_io(self, n: int, events: dict, who: str):
+        """The owgs_event_io of a call from events = {ident, ev_cap, rej_cap}: (struct, arrays to keep alive).  A cap
+        left out is the bound of include/owgs.h over what this binding registered."""
+        from ._lib import EVENT_MAX_FIXED, REJECT_TEXT_MAX, owgs_event_io
+        ident = np.ascontiguousarray(events["ident"], dtype=np.int32)
+        if len(ident) != n:
+            raise ValueError(f"{who}: events['ident'] needs one identity per item")
+        ev_cap, rej_cap = events.get("ev_cap"), events.get("rej_cap")
+        if ev_cap is None:
+            ev_cap = n * (EVENT_MAX_FIXED + getattr(self, "_ev_fixed", 0) + getattr(self, "_ev_piece", 0))
+        if rej_cap is None:
+            rej_cap = n * REJECT_TEXT_MAX
+        ev_out = C.create_string_buffer(max(int(ev_cap), 1))
+        rej_out = C.create_string_buffer(max(int(rej_cap), 1))
+        ev_off = np.zeros(n + 1, dtype=np.int64)
+        rej_off = np.zeros(n + 1, dtype=np.int64)
+        E = owgs_event_io(_p(ident if n else np.zeros(1, np.int32)), C.cast(ev_out, C.c_void_p), int(ev_cap),
+                          _p(ev_off), C.cast(rej_out, C.c_void_p), int(rej_cap), _p(rej_off), 0, 0, 0, 0)
+        return E, (ident, ev_out, rej_out, ev_off, rej_off)
+
+    @staticmethod
+    def _event_lists(n: int, E, keep):
+        """The two regions as lists of bytes by item; None for a region refused for capacity."""
+        _, ev_out, rej_out, ev_off, rej_off = keep
+        ev = None if E.ev_total > E.ev_cap else [ev_out.raw[ev_off[i]:ev_off[i + 1]] for i in range(n)]
+        rej = None if E.rej_total > E.rej_cap else [rej_out.raw[rej_off[i]:rej_off[i + 1]] for i in range(n)]
+        return ev, rej
+
+    def throttle_events(self, kind, verdict, rate_count, rate_limit, conc_count, conc_limit, ts_ms, ident,
+                        ev_cap: int | None = None, rej_cap: int | None = None):
+        """checkThrottleOverload's user event and error text per item (owgs_throttle_events) from the outputs of
+        `admit_batch`: (events, texts), two lists of bytes by item (b"" where the item has none).  A region over its cap
+        raises OwgsError(ERANGE) with `.events` (the two lists, None for the refused region), `.ev_total` and
+        `.rej_total`."""
+        kd = np.ascontiguousarray(kind, dtype=np.uint8)
+        n = len(kd)
+        vd = np.ascontiguousarray(verdict, dtype=np.uint8)
+        i32 = [np.ascontiguousarray(x, dtype=np.int32) for x in (rate_count, rate_limit, conc_count, conc_limit)]
+        ts = np.ascontiguousarray(ts_ms, dtype=np.int64)
+        if any(len(x) != n for x in [vd, ts] + i32):
+            raise ValueError("throttle_events: arrays of different lengths")
+        E, keep = self._event_io(n, {"ident": ident, "ev_cap": ev_cap, "rej_cap": rej_cap}, "throttle_events")
+        z = np.zeros(1, np.int64)
+        rc = self._L.owgs_throttle_events(self._h, n, _p(kd if n else z), _p(vd if n else z),
+                                          *[_p(x if n else z) for x in i32], _p(ts if n else z), C.byref(E))
+        if rc < 0:
+            e = OwgsError(rc, (self._L.owgs_last_error(self._h) or b"").decode())
+            if rc == ERANGE:
+                e.events = self._event_lists(n, E, keep)
+                e.ev_total, e.rej_total = int(E.ev_total), int(E.rej_total)
+            raise e
+        return self._event_lists(n, E, keep)
+
     def admit_batch(self, ns, kind, t_ms, rate_override=None, conc_override=None):
         """The entitlement throttle gate over a drained batch in array order (owgs_admit_batch): the per-minute rate
         throttle of each item's kind, then for an action that passed it the concurrent throttle.  kind: bit 0 trigger,
@@ -725,7 +799,7 @@ class GpuShardingContainerPoolBalancer:
 
     def invoke_activations(self, ns, kind, t_ms, actions, aids, tickets, time_limit_ms, now_ms: int,
                            rate_override=None, conc_override=None, seq=None, seq_base: int = 0,
-                           msgs: dict | None = None):
+                           msgs: dict | None = None, events: dict | None = None):
         """The throttle gate and publish for a drained batch in one call (owgs_invoke_activations): `admit_batch` over
         (ns, kind, t_ms, overrides), then `publish_activations` over the items that are actions with verdict ADMIT_OK,
         in array order, without the verdicts coming back in between.  Every other item gets invoker NOT_PUBLISHED,
@@ -734,7 +808,12 @@ class GpuShardingContainerPoolBalancer:
         Returns (verdict, rate_count, rate_limit, conc_count, conc_limit, invoker, flags, ticket, existed, summary),
         plus (bytes, out_off, out_order, topic_start) with msgs (out_order holds item indices).  summary: [0..7] as
         publish_activations, [8] admitted actions, [9] rate-rejected, [10] concurrent-rejected items, [11] admitted
-        triggers, [12] waits on the stream.  Errors, `.partial` (the ten values) and `.total` as publish_activations."""
+        triggers, [12] waits on the stream.  Errors, `.partial` (the ten values) and `.total` as publish_activations.
+        events = {"ident": one event identity per item, "ev_cap": .., "rej_cap": ..} (the caps optional) routes to
+        owgs_invoke_activations_events, timestamps t_ms: the result gains a last element (events, texts), two lists of
+        bytes by item as `throttle_events` returns them; summary [13] events, [14] texts written, [15] the event stage.
+        A region over its cap raises OwgsError(ERANGE) with `.partial` (the values without the events; with msgs the
+        messages included), `.events`, `.ev_total` and `.rej_total`: everything else is done, repeat `throttle_events`."""
         from ._lib import owgs_invoke_io
         h = np.ascontiguousarray(ns, dtype=np.int32)
         n = len(h)
@@ -763,6 +842,8 @@ class GpuShardingContainerPoolBalancer:
                             _p(tk if n else z32), _p(tl if n else z64), int(now_ms), _p(verdict), _p(rc_), _p(rl),
                             _p(cc), _p(cl), _p(inv), _p(fl), _p(ot), _p(ex))
         res = (verdict[:n], rc_[:n], rl[:n], cc[:n], cl[:n], inv[:n], fl[:n], ot[:n], ex[:n], summ)
+        if events is not None:
+            return self._invoke_events(n, io, res, msgs, events)
         if msgs is None:
             self._chk(self._L.owgs_invoke_activations(self._h, C.byref(io), None, None, _p(summ)))
             return res
@@ -777,6 +858,30 @@ class GpuShardingContainerPoolBalancer:
             raise e
         mm = mo.m
         return res + ((out.raw[:mo.total], off[:mm + 1], order[:mm], topic),)
+
+    def _invoke_events(self, n: int, io, res, msgs, events):
+        """invoke_activations through owgs_invoke_activations_events."""
+        summ = res[-1]
+        E, ekeep = self._event_io(n, events, "invoke_activations")
+        B = mo = keep = None
+        if msgs is not None:
+            B, mo, keep, (out, off, order, topic) = _msg_io(n, msgs, "invoke_activations")
+        rc = self._L.owgs_invoke_activations_events(self._h, C.byref(io), None if B is None else C.byref(B),
+                                                    None if mo is None else C.byref(mo), C.byref(E), _p(summ))
+        del keep
+        if msgs is not None and summ[6] == 3:
+            mm = mo.m
+            res = res + ((out.raw[:mo.total], off[:mm + 1], order[:mm], topic),)
+        if rc < 0:
+            e = OwgsError(rc, (self._L.owgs_last_error(self._h) or b"").decode())
+            if summ[6] >= 2:
+                e.partial = res
+                e.total = int(mo.total) if mo is not None else 0
+            if summ[15]:
+                e.events = self._event_lists(n, E, ekeep)
+                e.ev_total, e.rej_total = int(E.ev_total), int(E.rej_total)
+            raise e
+        return res + (self._event_lists(n, E, ekeep),)
 
     def release_invoker(self, invokers, actions) -> np.ndarray:
         """releaseInvoker (SCPB:327-331) per completion; returns release flags."""

@@ -378,6 +378,18 @@ struct owgs_ctx {
     DevBuf<uint32_t> m_key, m_key_sorted;
     DevBuf<ulonglong2> m_aid, m_cause;
     DevBuf<uint8_t> m_flags, m_temp;
+    // the throttle gate's user events (owgs_events.hip): the event source (a printed JSON string; unset until
+    // owgs_set_event_source), the identities' two pieces with their offsets, their device copies, the per-call scratch
+    // and byte regions, and the stand-alone call's inputs, output block and the pinned block it comes back in
+    std::string ev_src;
+    bool ev_src_set = false, ev_dirty = true;
+    std::vector<char> ei_a, ei_b;
+    std::vector<int64_t> ei_a_off{0}, ei_b_off{0};
+    DevBuf<char> e_src, e_ia, e_ib, e_ev_out, e_rej_out;
+    DevBuf<int64_t> e_ia_off, e_ib_off, e_ev_len, e_rej_len, e_ts;
+    DevBuf<int32_t> e_ident, e_i32;
+    DevBuf<uint8_t> e_kind, e_ver, e_temp, e_blk;
+    Pinned<> e_pin;
     int64_t h_now = INT64_MIN;
     // watched (invoker, fqn) pairs after a slot-state reset (owgs_watch.hip; w_cap == 0: none)
     DevBuf<uint32_t> w_keys, w_vals;

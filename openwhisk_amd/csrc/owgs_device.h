@@ -91,6 +91,56 @@ __device__ __forceinline__ int mod_fast(int x, int n, float rn) {
     return r;
 }
 
+// ------------------------------------------------------------------------------------------------ the serialisers
+// (owgs_msgs.hip, owgs_events.hip: decimal printing and the wave-cooperative copies)
+__device__ __forceinline__ unsigned long long pow10_at(int t) {  // 10^t, 0 <= t < 20
+    constexpr unsigned long long P[20] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull,
+        10000000ull, 100000000ull, 1000000000ull, 10000000000ull, 100000000000ull, 1000000000000ull, 10000000000000ull,
+        100000000000000ull, 1000000000000000ull, 10000000000000000ull, 100000000000000000ull, 1000000000000000000ull,
+        10000000000000000000ull};
+    return P[t];
+}
+
+__device__ __forceinline__ uint64_t magnitude(int64_t v) { return v < 0 ? (uint64_t)(-(v + 1)) + 1 : (uint64_t)v; }
+
+// decimal digits of |v| (+1 for the sign): t = floor(bit length * log10(2)) is the digit count or one less
+__device__ __forceinline__ int digits(int64_t v) {
+    const uint64_t u = magnitude(v);
+    const int t = ((64 - __clzll(u | 1)) * 1233) >> 12;
+    return max(t + (u >= pow10_at(t) ? 1 : 0), 1) + (v < 0);
+}
+
+// decimal digit of u at power r (0 = units): u split into three base-1e9 limbs by two constant divisions, then one
+// 32-bit division
+__device__ __forceinline__ int digit_at(uint64_t u, int r) {
+    const uint64_t q = u / 1000000000ull;
+    const uint32_t lo = (uint32_t)(u - q * 1000000000ull);
+    const uint64_t q2 = q / 1000000000ull;
+    const uint32_t mid = (uint32_t)(q - q2 * 1000000000ull), top = (uint32_t)q2;
+    const uint32_t x = r < 9 ? lo : r < 18 ? mid : top;
+    const uint32_t p = (uint32_t)pow10_at(r < 9 ? r : r < 18 ? r - 9 : r - 18);
+    return (int)((x / p) % 10u);
+}
+
+// wave-cooperative copy of len bytes
+__device__ __forceinline__ void wcopy(char* dst, const char* src, int64_t len, int lane) {
+    const int n = (int)len;  // a piece of one message: < 2^31 bytes
+    for (int j = lane; j < n; j += 64) dst[j] = src[j];
+}
+__device__ __forceinline__ void wlit(char* dst, const char* lit, int len, int lane) {
+    if (lane < len) dst[lane] = lit[lane];
+}
+
+// lane k of a wave writes character k (from the left) of v's decimal form at d; returns its length
+__device__ __forceinline__ int wput_dec(char* d, int64_t v, int lane) {
+    const int nd = digits(v);
+    if (lane < nd) {
+        if (v < 0 && lane == 0) d[0] = '-';
+        else d[lane] = (char)('0' + digit_at(magnitude(v), nd - 1 - lane));
+    }
+    return nd;
+}
+
 // ------------------------------------------------------------------------------------------------ chunked engine only
 // (the resident and the large-state engine use nothing below; it is here for the engine and the self-test that checks it)
 #define OWGS_CAPMAX 1024  // capacities are clamped: a lane's rank is < OWGS_WL

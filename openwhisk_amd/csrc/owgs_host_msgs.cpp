@@ -422,6 +422,193 @@ int owgs_publish_activations(owgs_ctx* c, const owgs_publish_io* io, const owgs_
                         out_summary, st);
 }
 
+// ------------------------------------------------------------------------------------------ throttle gate events
+int owgs_set_event_source(owgs_ctx* c, const char* json, int32_t len) {
+    if (!c || len < 0 || (len > 0 && !json)) return OWGS_EINVAL;
+    c->ev_src.assign(json ? json : "", (size_t)len);
+    c->ev_src_set = true;
+    c->ev_dirty = true;
+    return OWGS_OK;
+}
+
+int owgs_register_event_identities(owgs_ctx* c, int32_t n, const char* a_bytes, const int64_t* a_off,
+                                   const char* b_bytes, const int64_t* b_off, int32_t* out_first_id) {
+    if (!c || n < 0 || (n > 0 && (!a_off || !b_off))) return OWGS_EINVAL;
+    if (n > 0 && (a_off[0] != 0 || b_off[0] != 0))
+        return c->fail(OWGS_EINVAL, "event identities: offsets must start at 0");
+    for (int32_t i = 0; i < n; ++i)
+        if (a_off[i + 1] < a_off[i] || b_off[i + 1] < b_off[i])
+            return c->fail(OWGS_EINVAL, "event identities: offsets must be non-decreasing");
+    if (n > 0 && ((a_off[n] > 0 && !a_bytes) || (b_off[n] > 0 && !b_bytes)))
+        return c->fail(OWGS_EINVAL, "event identities: piece bytes missing");
+    if ((int64_t)c->ei_a_off.size() - 1 + n > INT32_MAX) return c->fail(OWGS_ERANGE, "too many event identities");
+    if (out_first_id) *out_first_id = (int32_t)c->ei_a_off.size() - 1;
+    for (int32_t i = 0; i < n; ++i) {
+        c->ei_a.insert(c->ei_a.end(), a_bytes + a_off[i], a_bytes + a_off[i + 1]);
+        c->ei_a_off.push_back((int64_t)c->ei_a.size());
+        c->ei_b.insert(c->ei_b.end(), b_bytes + b_off[i], b_bytes + b_off[i + 1]);
+        c->ei_b_off.push_back((int64_t)c->ei_b.size());
+    }
+    if (n > 0) c->ev_dirty = true;
+    return OWGS_OK;
+}
+
+// the checks of an owgs_event_io that need no context (before the context is looked at) ...
+static bool ev_io_ok(int32_t n, const owgs_event_io* ev) {
+    if (ev->ev_cap < 0 || ev->rej_cap < 0 || (ev->ev_cap > 0 && !ev->ev_out) || (ev->rej_cap > 0 && !ev->rej_out))
+        return false;
+    return n <= 0 || (ev->ident && ev->ev_off && ev->rej_off);
+}
+
+// ... and those that do: the source is set, every item's identity is registered
+static int ev_state_check(owgs_ctx* c, int32_t n, const owgs_event_io* ev) {
+    if (!c->ev_src_set) return c->fail(OWGS_EINVAL, "events: the event source is not set (owgs_set_event_source)");
+    const int32_t ni = (int32_t)c->ei_a_off.size() - 1;
+    for (int32_t i = 0; i < n; ++i)
+        if (ev->ident[i] < 0 || ev->ident[i] >= ni) return c->fail(OWGS_ENOENT, "events: unknown event identity");
+    return OWGS_OK;
+}
+
+static void ev_empty(owgs_event_io* ev) {
+    ev->ev_total = ev->rej_total = 0;
+    ev->n_events = ev->n_rejects = 0;
+    if (ev->ev_off) ev->ev_off[0] = 0;
+    if (ev->rej_off) ev->rej_off[0] = 0;
+}
+
+// bytes of the event section of an output block: ev_off and rej_off [n + 1], then the four count words
+static size_t ev_section_bytes(int32_t n) { return ((size_t)n + 1) * 16 + 16; }
+
+// Everything of the event stage that may wait or allocate: the source and identities on the device, the scratch, the
+// byte regions, the items' identities.  sec = the event section of the call's device block; A comes back complete but
+// for the gate's arrays and the timestamps.
+static int ev_prepare(owgs_ctx* c, int32_t n, const owgs_event_io* ev, uint8_t* sec, OwgsEventArgs& A, size_t& tb,
+                      hipStream_t st) {
+    if (c->ev_dirty) {
+        HIPCHK(c, upload(c->e_src, c->ev_src.data(), c->ev_src.size(), st));
+        HIPCHK(c, upload(c->e_ia, c->ei_a.data(), c->ei_a.size(), st));
+        HIPCHK(c, upload(c->e_ib, c->ei_b.data(), c->ei_b.size(), st));
+        HIPCHK(c, upload(c->e_ia_off, c->ei_a_off.data(), c->ei_a_off.size(), st));
+        HIPCHK(c, upload(c->e_ib_off, c->ei_b_off.data(), c->ei_b_off.size(), st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        c->ev_dirty = false;
+    }
+    tb = owgs_event_scratch_bytes(n);
+    HIPCHK(c, c->e_temp.reserve(tb));
+    HIPCHK(c, c->e_ev_len.reserve((size_t)n + 1));
+    HIPCHK(c, c->e_rej_len.reserve((size_t)n + 1));
+    HIPCHK(c, c->e_ev_out.reserve((size_t)std::max<int64_t>(ev->ev_cap, 1)));
+    HIPCHK(c, c->e_rej_out.reserve((size_t)std::max<int64_t>(ev->rej_cap, 1)));
+    HIPCHK(c, upload(c->e_ident, ev->ident, (size_t)n, st));
+    A.n = n;
+    A.ident = c->e_ident.p;
+    A.src = c->e_src.p;
+    A.src_len = (int32_t)c->ev_src.size();
+    A.ia = c->e_ia.p;
+    A.ia_off = c->e_ia_off.p;
+    A.ib = c->e_ib.p;
+    A.ib_off = c->e_ib_off.p;
+    A.ev_len = c->e_ev_len.p;
+    A.rej_len = c->e_rej_len.p;
+    A.ev_off = (int64_t*)sec;
+    A.rej_off = A.ev_off + n + 1;
+    A.cnt = (int32_t*)(A.rej_off + n + 1);
+    A.ev_out = c->e_ev_out.p;
+    A.ev_cap = ev->ev_cap;
+    A.rej_out = c->e_rej_out.p;
+    A.rej_cap = ev->rej_cap;
+    return OWGS_OK;
+}
+
+// the three steps, queued on st without a wait
+static int ev_queue(owgs_ctx* c, const OwgsEventArgs& A, size_t tb, hipStream_t st) {
+    HIPCHK(c, hipMemsetAsync(A.cnt, 0, 16, st));
+    HIPCHK(c, owgs_launch_events(&A, c->e_temp.p, tb, st));
+    return OWGS_OK;
+}
+
+// Once the block is in pinned memory (sec = its event section): the offsets, totals and counts handed out, the bytes of
+// every region that fitted queued for download (the caller waits).  stage = 1 done / 2 refused for capacity; written[2]
+// = the events / texts written.  Returns OWGS_ERANGE for a refused region.
+static int ev_collect(owgs_ctx* c, int32_t n, owgs_event_io* ev, const uint8_t* sec, int64_t* stage, int64_t* written,
+                      hipStream_t st) {
+    const size_t ob = ((size_t)n + 1) * 8;
+    memcpy(ev->ev_off, sec, ob);
+    memcpy(ev->rej_off, sec + ob, ob);
+    int32_t cnt[4];
+    memcpy(cnt, sec + 2 * ob, 16);
+    ev->ev_total = ev->ev_off[n];
+    ev->rej_total = ev->rej_off[n];
+    ev->n_events = cnt[0];
+    ev->n_rejects = cnt[1];
+    const bool ev_fits = ev->ev_total <= ev->ev_cap, rej_fits = ev->rej_total <= ev->rej_cap;
+    if (ev_fits && ev->ev_total)
+        HIPCHK(c, hipMemcpyAsync(ev->ev_out, c->e_ev_out.p, (size_t)ev->ev_total, hipMemcpyDeviceToHost, st));
+    if (rej_fits && ev->rej_total)
+        HIPCHK(c, hipMemcpyAsync(ev->rej_out, c->e_rej_out.p, (size_t)ev->rej_total, hipMemcpyDeviceToHost, st));
+    written[0] = ev_fits ? cnt[0] : 0;
+    written[1] = rej_fits ? cnt[1] : 0;
+    *stage = ev_fits && rej_fits ? 1 : 2;
+    if (ev_fits && rej_fits) return OWGS_OK;
+    return c->fail(OWGS_ERANGE, "events: a region's capacity is below the batch's bytes (see ev_total / rej_total)");
+}
+
+// checkThrottleOverload's event and error text (Entitlement.scala:383-420) for n items from the gate's outputs in host
+// arrays: the pure function of include/owgs.h, no state change.
+int owgs_throttle_events(owgs_ctx* c, int32_t n, const uint8_t* kind, const uint8_t* verdict,
+                         const int32_t* rate_count, const int32_t* rate_limit, const int32_t* conc_count,
+                         const int32_t* conc_limit, const int64_t* ts_ms, owgs_event_io* ev) {
+    if (!c || !ev || n < 0 || !ev_io_ok(n, ev)) return OWGS_EINVAL;
+    if (n > 0 && (!kind || !verdict || !rate_count || !rate_limit || !conc_count || !conc_limit || !ts_ms))
+        return OWGS_EINVAL;
+    for (int32_t i = 0; i < n; ++i) {
+        if (verdict[i] > OWGS_ADMIT_CONCURRENT) return c->fail(OWGS_EINVAL, "events: verdict outside 0..2");
+        if (kind[i] & ~(OWGS_ADMIT_TRIGGER | OWGS_ADMIT_RATE_OVERRIDE | OWGS_ADMIT_CONC_OVERRIDE))
+            return c->fail(OWGS_EINVAL, "events: reserved kind bits");
+    }
+    int rc = ev_state_check(c, n, ev);
+    if (rc) return rc;
+    if (n == 0) {
+        ev_empty(ev);
+        return OWGS_OK;
+    }
+    OWGS_ENTER(c);
+    {
+        const int ro_ = order_on(c, c->stream);
+        if (ro_) return ro_;
+    }
+    hipStream_t st = c->stream;
+    const size_t N = (size_t)n, sec_bytes = ev_section_bytes(n);
+    if (c->e_pin.bytes < sec_bytes) HIPCHK(c, c->e_pin.reserve(sec_bytes * 2, hipHostMallocDefault));
+    HIPCHK(c, c->e_blk.reserve(sec_bytes));
+    OwgsEventArgs A{};
+    size_t tb = 0;
+    rc = ev_prepare(c, n, ev, c->e_blk.p, A, tb, st);
+    if (rc) return rc;
+    HIPCHK(c, upload(c->e_kind, kind, N, st));
+    HIPCHK(c, upload(c->e_ver, verdict, N, st));
+    HIPCHK(c, c->e_i32.reserve(4 * N));
+    const int32_t* src32[4] = {rate_count, rate_limit, conc_count, conc_limit};
+    for (int k = 0; k < 4; ++k)
+        HIPCHK(c, hipMemcpyAsync(c->e_i32.p + k * N, src32[k], N * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, upload(c->e_ts, ts_ms, N, st));
+    A.kind = c->e_kind.p;
+    A.verdict = c->e_ver.p;
+    A.rate_count = c->e_i32.p;
+    A.rate_limit = c->e_i32.p + N;
+    A.conc_count = c->e_i32.p + 2 * N;
+    A.conc_limit = c->e_i32.p + 3 * N;
+    A.ts = c->e_ts.p;
+    rc = ev_queue(c, A, tb, st);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->e_pin.p, c->e_blk.p, sec_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    int64_t stage = 0, written[2];
+    rc = ev_collect(c, n, ev, (const uint8_t*)c->e_pin.p, &stage, written, st);
+    HIPCHK(c, hipStreamSynchronize(st));
+    return rc;
+}
+
 // ------------------------------------------------------------------------------------------ gated publish
 // The engine step of owgs_invoke_activations on an on-chip context: publish_device without its uploads.  The admitted
 // actions are in d_a (and d_seq) and their count m only on the device, as the batch offsets {0, m} in d_off; n bounds
@@ -444,11 +631,13 @@ static int invoke_engine(owgs_ctx* c, int32_t n, bool has_seq, uint64_t seq_base
 // EntitlementProvider.checkThrottles (Entitlement.scala:197-202, 354-381) and, for what it admits,
 // ShardingContainerPoolBalancer.publish (SCPB:257-317) for a drained batch (the semantics are in
 // include/owgs.h).  On an on-chip context nothing below waits between queueing the gate and the one block copy.
-int owgs_invoke_activations(owgs_ctx* c, const owgs_invoke_io* io, const owgs_msg_batch* msgs, owgs_msg_out* mo,
-                            int64_t out_summary[16]) {
+// ev: the event stage of owgs_invoke_activations_events, or NULL.
+static int invoke_run(owgs_ctx* c, const owgs_invoke_io* io, const owgs_msg_batch* msgs, owgs_msg_out* mo,
+                      owgs_event_io* ev, int64_t out_summary[16]) {
     if (!c || !io || !out_summary) return OWGS_EINVAL;
     const int32_t n = io->n;
     if (n < 0 || (msgs == nullptr) != (mo == nullptr)) return OWGS_EINVAL;
+    if (ev && !ev_io_ok(n, ev)) return OWGS_EINVAL;
     if (n > 0 && (!io->ns || !io->kind || !io->t_ms || !io->action || !io->aid || !io->ticket || !io->time_limit_ms ||
                   !io->out_verdict || !io->out_rate_count || !io->out_rate_limit || !io->out_conc_count ||
                   !io->out_conc_limit || !io->out_invoker || !io->out_flags || !io->out_ticket || !io->out_existed))
@@ -481,8 +670,16 @@ int owgs_invoke_activations(owgs_ctx* c, const owgs_invoke_io* io, const owgs_ms
         if (!(io->kind[i] & OWGS_ADMIT_TRIGGER) && !registered(c, 1, io->action + i))
             return c->fail(OWGS_ENOENT, "unknown action");
     if (!ns_known(c, n, io->ns)) return c->fail(OWGS_ENOENT, "unknown namespace");
+    if (ev) {
+        const int re = ev_state_check(c, n, ev);
+        if (re) return re;
+    }
     for (int k = 0; k < 16; ++k) out_summary[k] = 0;
     if (n == 0) {
+        if (ev) {
+            ev_empty(ev);
+            out_summary[15] = 1;
+        }
         if (mo) {
             mo->total = 0;
             mo->m = 0;
@@ -505,9 +702,17 @@ int owgs_invoke_activations(owgs_ctx* c, const owgs_invoke_io* io, const owgs_ms
     int rc = act_reserve(c, n);
     if (!rc && msgs) rc = msg_templates_upload(c, st);
     if (rc) return rc;
-    const size_t hdr_bytes = (size_t)OWGS_PUB_HDR * 8, blk_bytes = hdr_bytes + N * 27;
+    // with events the block carries their section behind the nine arrays: the same one copy brings both back
+    const size_t hdr_bytes = (size_t)OWGS_PUB_HDR * 8, ev_at = (hdr_bytes + N * 27 + 7) & ~(size_t)7,
+                 blk_bytes = ev ? ev_at + ev_section_bytes(n) : hdr_bytes + N * 27;
     if (c->p_pin.bytes < blk_bytes) HIPCHK(c, c->p_pin.reserve(blk_bytes * 2, hipHostMallocDefault));
     HIPCHK(c, c->p_blk.reserve(blk_bytes));
+    OwgsEventArgs E{};
+    size_t ev_tb = 0;
+    if (ev) {
+        rc = ev_prepare(c, n, ev, c->p_blk.p + ev_at, E, ev_tb, st);
+        if (rc) return rc;
+    }
     HIPCHK(c, c->p_placed.reserve(N));
     if (msgs) HIPCHK(c, c->p_minv.reserve(N));
     int32_t bits = 1;
@@ -543,7 +748,27 @@ int owgs_invoke_activations(owgs_ctx* c, const owgs_invoke_io* io, const owgs_ms
     G.out_conc_count = b_cc;
     G.out_conc_limit = b_cl;
     HIPCHK(c, owgs_launch_admit(c->k_act.p, bits, c->q_temp.p, tb, c->q_key.p, c->q_idx0.p, c->q_idx1.p, &G, st));
+    // the events read only the gate's outputs: queued right behind it, they do not wait for the engine
+    if (ev) {
+        E.kind = c->k_kind.p;
+        E.verdict = b_ver;
+        E.rate_count = b_rc;
+        E.rate_limit = b_rl;
+        E.conc_count = b_cc;
+        E.conc_limit = b_cl;
+        E.ts = c->k_off.p;
+        rc = ev_queue(c, E, ev_tb, st);
+        if (rc) return rc;
+    }
     int64_t waits = 0;
+    // the event section of the pinned block handed out and the regions' bytes downloaded (not counted in [12], like the
+    // message bytes); wait = false leaves the wait for the download to the caller
+    auto events_out = [&](bool wait) {
+        int re = ev_collect(c, n, ev, (const uint8_t*)c->p_pin.p + ev_at, &out_summary[15], &out_summary[13], st);
+        if (wait && hipStreamSynchronize(st) != hipSuccess && re != OWGS_EDEVICE)
+            re = c->fail(OWGS_EDEVICE, "invoke: the download of the events failed");
+        return re;
+    };
     // the five gate outputs from the pinned block (valid whenever the gate ran, whatever happens after it)
     auto gate_out = [&]() {
         const char* P = (const char*)c->p_pin.p + hdr_bytes;
@@ -568,6 +793,7 @@ int owgs_invoke_activations(owgs_ctx* c, const owgs_invoke_io* io, const owgs_ms
             hipStreamSynchronize(st) == hipSuccess) {
             gate_out();
             out_summary[12] = waits + 1;
+            if (ev) (void)events_out(true);
         }
         return code;
     };
@@ -665,6 +891,24 @@ int owgs_invoke_activations(owgs_ctx* c, const owgs_invoke_io* io, const owgs_ms
     out_summary[12] = waits;
     const char* P = (const char*)c->p_pin.p + hdr_bytes;
     const PublishBlock B{P + 16 * N, P + 20 * N, P + 25 * N, P + 26 * N};
-    return publish_tail(c, "invoke", n, B, io->out_invoker, io->out_flags, io->out_ticket, io->out_existed, msgs, mo,
-                        out_summary, st);
+    const int re = ev ? events_out(false) : OWGS_OK;
+    const std::string ev_err = re ? c->err : std::string();
+    rc = publish_tail(c, "invoke", n, B, io->out_invoker, io->out_flags, io->out_ticket, io->out_existed, msgs, mo,
+                      out_summary, st);
+    if (!ev) return rc;
+    // the event bytes were queued before the message bytes: one wait covers both.  The message stage's code wins.
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = c->fail(OWGS_EDEVICE, "invoke: the download of the events failed");
+    if (rc || !re) return rc;
+    c->err = ev_err;
+    return re;
+}
+
+int owgs_invoke_activations(owgs_ctx* c, const owgs_invoke_io* io, const owgs_msg_batch* msgs, owgs_msg_out* mo,
+                            int64_t out_summary[16]) {
+    return invoke_run(c, io, msgs, mo, nullptr, out_summary);
+}
+
+int owgs_invoke_activations_events(owgs_ctx* c, const owgs_invoke_io* io, const owgs_msg_batch* msgs,
+                                   owgs_msg_out* mo, owgs_event_io* ev, int64_t out_summary[16]) {
+    return invoke_run(c, io, msgs, mo, ev, out_summary);
 }

@@ -767,6 +767,33 @@ struct OwgsAdmitArgs {
     int32_t *out_rate_count, *out_rate_limit, *out_conc_count, *out_conc_limit;
 };
 
+// The throttle gate's user events and rejection texts (owgs_events.hip); every pointer is device memory.  The outputs
+// are by item: ev_off / rej_off [n + 1] (entry n = the bytes needed), cnt = {items with an event, items with a text,
+// refused regions (bit0 events, bit1 texts: the bytes needed exceed the cap, nothing of that region is written), 0}.
+#define OWGS_EVT_REFUSED_EV 1
+#define OWGS_EVT_REFUSED_REJ 2
+struct OwgsEventArgs {
+    int32_t n;
+    const uint8_t* kind;         // [n] bit0: a trigger
+    const uint8_t* verdict;      // [n] OWGS_ADMIT_*
+    const int32_t *rate_count, *rate_limit, *conc_count, *conc_limit;  // [n] the gate's outputs
+    const int64_t* ts;           // [n] the event's timestamp
+    const int32_t* ident;        // [n] event identity, below the registered count (checked on the host)
+    const char* src;             // the event source, a printed JSON string
+    int32_t src_len;
+    const char* ia;              // identity pieces A / B and their offsets
+    const int64_t* ia_off;
+    const char* ib;
+    const int64_t* ib_off;
+    int64_t *ev_len, *rej_len;   // scratch [n + 1]
+    int64_t *ev_off, *rej_off;   // out [n + 1]
+    int32_t* cnt;                // out [4], zero before the launch
+    char* ev_out;
+    int64_t ev_cap;
+    char* rej_out;
+    int64_t rej_cap;
+};
+
 // ActivationMessage serialisation + topic fan-out (owgs_msgs.hip); every pointer is device memory
 struct OwgsMsgArgs {
     int32_t n;

@@ -105,6 +105,8 @@ extern "C" hipError_t owgs_launch_msg_plan(const OwgsMsgArgs* a, int32_t bits, v
                                            uint32_t* key_sorted, int32_t* iota, int64_t* len_sorted, int32_t* cnt,
                                            hipStream_t st);
 extern "C" hipError_t owgs_launch_msg_write(const OwgsMsgArgs* a, hipStream_t st);
+extern "C" size_t owgs_event_scratch_bytes(int32_t n);
+extern "C" hipError_t owgs_launch_events(const OwgsEventArgs* a, void* temp, size_t temp_bytes, hipStream_t st);
 extern "C" size_t owgs_engine_lds_bytes(int n_slots, int pool_mode, int n_ids, int nm, int nb, int n_actions);
 // the narrow geometry (owgs_engine_narrow.hip): same ABI, 7 x 32-lane chunks
 extern "C" size_t owgs_engine_lds_bytes_narrow(int n_slots, int pool_mode, int n_ids, int nm, int nb, int n_actions);
