@@ -956,7 +956,9 @@ int owgs_selftest(owgs_ctx* ctx);
 
 /* Engine counters of the last engine launch (diagnostics): [0] resolution passes, [1] walk probes, [2] overload
  * fallbacks, [3] wave-cooperative long walks, [4] chunks, [5] passes that stopped before the chunk end,
- * [31] lanes re-decided inside their pass; [8..15] per-phase shader cycles in the diagnostic build
+ * [31] lanes re-decided inside their pass; [32] NestedSemaphore entries, absent when their lanes speculated, that the
+ * I/O wave found or inserted ahead of the commit, [33] committing lanes that found or inserted theirs themselves
+ * (the entry pre-find); [8..15] per-phase shader cycles in the diagnostic build
  * (libowgs_prof.so).  On a context that runs on the large-state engine the slots [40..43] (cycles of its releases,
  * group speculation, kept decisions, decisions decided alone) and [46], [47] (decisions kept from the speculation /
  * decided alone) are not the last launch's: they are totals since the context was created (owgs_large_stats). */

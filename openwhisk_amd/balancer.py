@@ -996,6 +996,13 @@ class GpuShardingContainerPoolBalancer:
     def selftest(self):
         self._chk(self._L.owgs_selftest(self._h))
 
+    def entry_stats(self) -> dict:
+        """The last engine launch's entry pre-find: concurrency-map entries, absent when their lanes
+        speculated, that the I/O wave found or inserted / that the committing lanes found or inserted themselves."""
+        out = (C.c_uint64 * 48)()
+        self._chk(self._L.owgs_read_stats(self._h, out, 48))
+        return {"prefound": out[32], "lane_found": out[33]}
+
     def stats(self) -> dict:
         out = (C.c_uint64 * 48)()
         self._chk(self._L.owgs_read_stats(self._h, out, 48))

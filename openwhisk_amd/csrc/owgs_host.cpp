@@ -386,7 +386,9 @@ void base_args(owgs_ctx* c, OwgsEngineArgs& A) {
     A.rng_seed = c->cfg.rng_seed;
     A.stats = c->d_stats.p;
     A.err = c->d_err.p;
-    A.opts = (env_opts().opts & ~OWGS_OPT_WIDE_MEM) | (c->wide_mem ? OWGS_OPT_WIDE_MEM : 0);
+    // (watched pairs can hold live entries that count zero: no pre-find placeholders beside them)
+    A.opts = (env_opts().opts & ~OWGS_OPT_WIDE_MEM) | (c->wide_mem ? OWGS_OPT_WIDE_MEM : 0) |
+             (c->w_cap > 0 ? OWGS_OPT_NO_PREFIND : 0);
     A.hwords = c->grp_hwords;
     A.hstride = c->grp_hstride;
     A.trace = nullptr;

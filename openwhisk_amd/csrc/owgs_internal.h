@@ -111,6 +111,9 @@
 // count has to stay below 2^22 MB for the engine's capacities to be exact; the host sends a context with such limits
 // and such a slot to the large-state engine
 #define OWGS_OPT_WIDE_MEM 2
+// OwgsEngineArgs.opts: the launch runs without the entry pre-find.  Set while watched pairs exist
+// (DESIGN.md 3.1): their entries can count exactly zero and stay live, which the pre-find's placeholders would alias
+#define OWGS_OPT_NO_PREFIND 4
 
 // LDS permits of identity pools carry the usable flag: an unusable invoker's permits are stored + OWGS_PENC, so one
 // LDS read gives both (usable permits < OWGS_PLIM <= unusable ones); HBM holds the plain values
@@ -124,7 +127,9 @@
 #define OWGS_ST_LONG 3
 #define OWGS_ST_CHUNKS 4
 #define OWGS_ST_STOPS 5
-#define OWGS_NSTATS 48  // 0-7 counters, 8-15 profile-build phase cycles, 16-31 profile-build walk counters,
+#define OWGS_ST_PREFOUND 32   // absent concurrency-map entries found or inserted by the I/O wave (entry pre-find)
+#define OWGS_ST_LANEFOUND 33  // writers that ran the find-or-insert themselves (entry absent when they speculated)
+#define OWGS_NSTATS 48  // 0-7 counters, 8-15 profile-build phase cycles, 16-31 profile-build walk counters, 32-33 above,
                         // 40-42 profile-build kernel cycles (state load, batches, write-back); 46-47 (host-side, large-
                         // state contexts) decisions kept from the group speculation / decided alone
 
@@ -197,7 +202,8 @@ struct OwgsEngineArgs {
     unsigned long long* stats;   // this launch's counters (zero when it starts)
     unsigned long long* stats_next;  // the next launch's counter block: zeroed at the end of this one (no fill launch)
     int32_t* err;
-    int32_t opts;                // bit0 (diagnostics, env OWGS_OPTS) = no hot-action rank tables; OWGS_OPT_WIDE_MEM
+    int32_t opts;                // bit0 (diagnostics, env OWGS_OPTS) = no hot-action rank tables; OWGS_OPT_WIDE_MEM;
+                                 // OWGS_OPT_NO_PREFIND (watched pairs, or env OWGS_OPTS bit 2)
     int32_t cw;                  // chunk width of this replay (<= OWGS_WL)
     unsigned long long* trace;   // diagnostic build only (-DOWGS_TRACE): [waves][OWGS_TRACE_CAP] barrier timeline
     int32_t feat;                // engine code paths this launch needs (OWGS_F_*): picks the compiled specialisation

@@ -154,6 +154,19 @@ __device__ __forceinline__ unsigned long long memtime_pinned() {
 #endif
 #define CFT_N (1 << CFT_LOG2)
 #define SC_N (SC_CFT + 2 * CFT_N)
+// entry pre-find: the lanes whose concurrency-table entry was absent when they speculated queue its key
+// in the tentative phase; the I/O wave, idle during validation, finds or inserts the first PF_CAP of them (one round,
+// one key per lane) and leaves each entry's index in the queue for the commit.  The queue lives in the hot-walk
+// scratch (hscr: dead between barrier 2 and the end of the pass), its counter in the padding behind the SC_N scalars.
+#ifndef PF_CAP
+#define PF_CAP 64
+#endif
+#define PF_QCAP 256  // queue entries {key, index or -1}; lanes beyond it keep the commit's own find-or-insert
+#define SC_PFN SC_N  // keys queued in this pass (may count past PF_QCAP)
+#define SC_PFOFF (SC_N + 1)  // the launch runs without the pre-find (watched pairs exist: OWGS_OPT_NO_PREFIND)
+static_assert(PF_CAP >= 1 && PF_CAP <= 64, "one round of the I/O wave, one key per lane");
+static_assert((((4u * SC_N) + 15u) & ~15u) >= 4u * (SC_N + 2), "SC_PFN and SC_PFOFF sit in the scalars' padding");
+static_assert(8u * PF_QCAP <= 4u * 64 * (OWGS_EW + 1), "the pre-find queue fits the hot-walk scratch");
 
 // hot actions: every action with >= HOT_MIN lanes in a chunk gets a slot (assigned by the pre-pass; a concurrent
 // action only when no lane of the chunk shares its fqn@version with another action); per pass one wave walks its
@@ -1065,6 +1078,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
     int32_t* hflag = (int32_t*)(L + LY_HDIR + 20u * NHOT);
     uint2* htab = (uint2*)(L + LY_HTAB);
     int32_t* hscr = (int32_t*)(L + LY_HSCR);
+    uint2* pfq = (uint2*)(L + LY_HSCR);  // the pre-find queue: the same bytes between barrier 2 and the end of a pass
     const uint32_t* stgL = (const uint32_t*)(L + LY_STGL);
     uint32_t* rc = (uint32_t*)(L + LY_RC);
     int32_t* sc = (int32_t*)(L + LY_SC);
@@ -1091,6 +1105,10 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
     if (tid < SC_N)
         sc[tid] = (tid == SC_IRR || tid == SC_RRISK) ? 0
                                                      : ((tid < 4 || tid >= SC_CFT) ? OWGS_WL : (tid < 6 ? (int)0x80000000 : 0));
+    if (kConc && tid == 0) {
+        sc[SC_PFN] = 0;
+        sc[SC_PFOFF] = (A.opts & OWGS_OPT_NO_PREFIND) ? 1 : 0;
+    }
     // the capacity form's domain (owgs_divq.h): permits below 2^22 MB, or memory limits of at most
     // OWGS_DIVQ_MEM_ANY MB (every larger quotient is clamped).  The host keeps states with both off this engine; one
     // that arrives all the same is refused before anything is touched (OWGS_ERR_PERMITS)
@@ -1208,6 +1226,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
 
     uint32_t st_pass = 0, st_probe = 0, st_fb = 0, st_long = 0, st_chunk = 0, st_stop = 0, st_gprobe = 0, st_glane = 0;
     uint32_t st_ext = 0;  // in-pass re-decisions (I/O wave)
+    uint32_t st_pf = 0, st_pl = 0;  // absent entries resolved by the I/O wave / by the committing lane itself
 #ifdef OWGS_EXT_PROF
     u64 xp_cyc = 0, xp_rounds = 0, xp_scans = 0, xp_ph[4] = {0, 0, 0, 0};
 #endif
@@ -1535,13 +1554,14 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
         if (kConc && ((sc[SC_USED] > OWGS_CTC / 2 && sc[SC_USED] >= sc[SC_CLAST] + OWGS_CTC / 8) ||
                       (A.ovf.cap > 0 && sc[SC_OVF] > A.ovf.cap / 2))) {
             const bool had_ovf = sc[SC_OVF] > 0;
+            const bool pf_live = sc[SC_PFOFF] == 0;  // zero-valued entries are the pre-find's placeholders: dropped
             if (!io) {
                 for (int ix = tid; ix < OWGS_CTC; ix += OWGS_ENT) {
-                    const uint32_t k = ct[ix].x;
-                    if (k != 0u && k != OWGS_CT_TOMB) {
+                    const uint2 e = ct[ix];
+                    if (e.x != 0u && e.x != OWGS_CT_TOMB && !(pf_live && e.y == 0u)) {
                         const int j = atomicAdd(&sc[SC_NLIVE], 1);
-                        A.ct_tmp[2 * j] = k;
-                        A.ct_tmp[2 * j + 1] = ct[ix].y;
+                        A.ct_tmp[2 * j] = e.x;
+                        A.ct_tmp[2 * j + 1] = e.y;
                     }
                 }
                 if (had_ovf)
@@ -1743,6 +1763,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
             while (f < len) {
                 ++st_pass;
                 const bool ovf_on = kConc && OWGS_OVF && sc[SC_OVF] > 0;  // overflow keys exist: lookups fall through (uniform)
+                const bool pf_go = kConc && !ovf_on && sc[SC_PFOFF] == 0;  // absent entries are pre-found (uniform)
 #ifdef OWGS_PROFILE
                 const u64 tpass0 = memtime_pinned();
 #ifdef OWGS_PROF_LATER
@@ -2528,6 +2549,27 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                     else if (kind == K_FALLBACK) cons = c0v >= 1 ? 0 : mem;
                     else cons = (ks < c0v) ? 0 : (small_mod(ks - c0v, maxc) == 0 ? mem : 0);
                 }
+                // ------------------------------------------------ entry pre-find: queue the absent entries' keys
+                // A lane whose entry was absent when it speculated (a kept lane: in every pass until it commits)
+                // queues {key, -1}; the I/O wave resolves the first PF_CAP during validation, and the lane keeps its
+                // queue position in cidx (-2 - position) until the commit reads the index back.  A wave takes its
+                // range of the queue by ballot and one LDS atomic, as the long-walk queue does.
+                if (kConc && !io) {
+                    if (cidx < -1) cidx = -1;  // (a kept lane's position in an earlier pass's queue)
+                    const bool pf = pf_go && part && maxc > 1 && cidx < 0;
+                    const u64 pm = __ballot(pf);
+                    if (pm) {
+                        int qb = 0;
+                        if (lane == 0) qb = atomicAdd(&sc[SC_PFN], __popcll(pm));
+                        qb = __builtin_amdgcn_readfirstlane(qb);
+                        const int q = qb + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32),
+                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
+                        if (pf && q < PF_QCAP) {
+                            pfq[q] = make_uint2(ct_key(t, slot), 0xFFFFFFFFu);
+                            cidx = -2 - q;
+                        }
+                    }
+                }
                 // ------------------------------------------------ bucket totals
                 // every lane tentatively takes its memory from its target's permits: after the barrier P[t] is the
                 // frontier permits minus the consumption of ALL lanes of the pass at t (the commit keeps it, the
@@ -2548,6 +2590,25 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                 LDS_SYNC_T(3);
                 // (fallback+buckets accrue to PT(6));
                 PT(3);
+                // ------------------------------------------------ entry pre-find: the I/O wave finds or inserts
+                // Nothing reads or writes ct between this barrier and the next, and the I/O wave holds no lanes: one
+                // round over the first PF_CAP queued keys (several lanes with one key: the CAS loser rescans and finds
+                // it).  An entry inserted here keeps value 0 until its lane commits -- every lookup reads that as
+                // absent.  Near the primary's fill nothing is touched: the commit's own path decides between the
+                // primary and the overflow.  LDS only (no vector memory access: the prefetch stream stays in flight).
+                if (kConc && io) {
+                    const int npf = min(sc[SC_PFN], PF_CAP);
+                    if (npf > 0 && sc[SC_USED] + npf <= OWGS_CT_LDS_FILL) {  // (uniform)
+                        int fresh = 0, ix = -1;
+                        if (lane < npf) {
+                            ix = ct_upsertv(ct, pfq[lane].x, &fresh);
+                            pfq[lane].y = (uint32_t)ix;
+                        }
+                        const u64 fm = __ballot(fresh != 0);
+                        if (fm && lane == 0) atomicAdd(&sc[SC_USED], __popcll(fm));
+                        st_pf += (uint32_t)__popcll(__ballot(ix >= 0));  // (counted by lane 0 at the end)
+                    }
+                }
                 // ------------------------------------------------ validate: known to fit?
                 bool nf = false;
 #ifdef OWGS_STOP_REASONS
@@ -2866,7 +2927,14 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                             if (ops1 > OWGS_MAX_OPS) err |= OWGS_ERR_OPS;
                             int ix = cidx;
                             const uint32_t key = ct_key(t, slot), nv = ct_val(c1, ops1);
+                            // queued for the pre-find: the entry's index, or -1 (beyond PF_CAP, table near its fill)
+                            if (ix < -1) ix = (int)pfq[-2 - ix].y;
                             if (ix < 0) {  // absent when speculated (a kept lane's group may have created it since)
+#ifdef OWGS_PROF_ENTRY  // diagnostic: this branch's cycles | passes << 40, waves 0-4 / 5 / 6 -> stats[34 / 35 / 36]
+                                const u64 te0 = memtime_pinned();
+                                const u64 tem = __ballot(true);
+#endif
+                                ++st_pl;
                                 uint32_t vv;
                                 if (ovf_on) {
                                     const int oj = ovf_find(A.ovf, key, &vv);
@@ -2888,6 +2956,13 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                                         atomicAdd(&sc[SC_OVF], 1);
                                     }
                                 }
+#ifdef OWGS_PROF_ENTRY
+                                {
+                                    const u64 te1 = memtime_pinned();
+                                    if (lane == ffs64(tem))
+                                        atomicAdd(&A.stats[34 + max(wave, 4) - 4], (1ull << 40) | (te1 - te0));
+                                }
+#endif
                             }
                             if (ix < 0) err |= OWGS_ERR_CTAB_FULL;
                             else if (ix < OWGS_CTC) ct[ix].y = nv;
@@ -2932,6 +3007,7 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
                 if (tid == 0) {
                     sc[SC_LQN] = 0;  // the queue of this pass was drained before barrier 2
                     sc[SC_LQH] = 0;
+                    if (kConc) sc[SC_PFN] = 0;  // (only the I/O wave reads it, before barrier 4)
                     sc[SC_NHOT] = 0;  // read at the chunk start, before this pass's barriers
                     sc[SC_LMIN + (par ^ 1)] = OWGS_WL;
                     if (l < len) ++st_stop;
@@ -2973,9 +3049,11 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
     }
     if (tid == 0 && A.ovf.cap > 0) __hip_atomic_store(A.ovf.cnt, sc[SC_OVF], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (tid == 0 && A.ct_clast) *A.ct_clast = sc[SC_CLAST];
+    // (a placeholder the pre-find left behind leaves as a deleted entry: outside a launch no live entry counts zero)
+    const bool pf_live = kConc && sc[SC_PFOFF] == 0;
     for (int i = tid; i < OWGS_CTC; i += OWGS_NT) {
         const uint2 e = ct[i];
-        A.ct_keys[i] = e.x;
+        A.ct_keys[i] = (pf_live && e.x != 0u && e.y == 0u) ? OWGS_CT_TOMB : e.x;
         A.ct_vals[i] = e.y;
     }
     if (A.out_copy_n16 > 0) {  // (uniform) this launch's outputs (HBM) into the caller's pinned block, 16 B per store
@@ -3034,6 +3112,10 @@ __device__ __forceinline__ void owgs_engine_body(const OwgsEngineArgs& A) {
         }
 #endif
         if (io && lane == 0) atomicAdd(&A.stats[31], (u64)st_ext);  // (the upper half stays 0: it counted a retired path)
+        if (kConc) {  // the entry pre-find: resolved by the I/O wave / writers that ran the find-or-insert themselves
+            if (io && lane == 0) atomicAdd(&A.stats[OWGS_ST_PREFOUND], (u64)st_pf);
+            if (!io && st_pl) atomicAdd(&A.stats[OWGS_ST_LANEFOUND], (u64)st_pl);
+        }
 #ifdef OWGS_EXT_PROF
         if (io && lane == 0) {
             atomicAdd(&A.stats[28], xp_cyc);

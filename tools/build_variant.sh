@@ -16,5 +16,5 @@ wait $p1 && wait $p2 && wait $p3
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o variants/libowgs_$1.so build/variants/k_$1.o \
   build/variants/n_$1.o build/owgs_watch.o build/owgs_fused.o build/owgs_resident.o build/owgs_seq.o build/owgs_state.o build/owgs_acks.o \
   build/owgs_expire.o build/owgs_inflight.o build/owgs_health.o build/owgs_feeds.o build/owgs_msgs.o build/owgs_publish.o \
-  build/owgs_invoke.o \
+  build/owgs_invoke.o build/owgs_events.o \
   $(for h in $HOST; do echo build/variants/h_$1_$h.o; done)
